@@ -14,6 +14,14 @@ Synthetic data is generated on the device (torch Philox), resident in HBM before
 timed region.  One step = one decode launch over the whole per-GPU batch.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload awgn|deletion|qary] [--batch B]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (the error counters
+and the roofline figures in it come from those same steps).  --dump-outputs DIR then also writes
+what the last timed step returned (the packed decisions a caller of the decoder receives) as
+DIR/<name>.npy; the inputs depend on the arguments alone, so two builds compare output for
+output.  --full adds the legs that take runs of their own: the end-to-end Monte-Carlo line
+(mc_end_to_end) and the CPU baseline (cpu_baseline).
 
 Multi-GPU: one process per GPU.  Under torch.distributed.run (WORLD_SIZE set) this
 process is one rank; started directly with --gpus N > 1 it launches the N ranks itself
@@ -132,6 +140,11 @@ class Awgn:
     def errors(self):
         d = sc.unpack(self.outs[0], self.K)
         return mc.error_counts(d, sc.unpack(self.info_w, self.K))
+
+    def outputs(self):
+        """What step() hands its caller: the packed words, codewords along the last axis."""
+        names = ("info_words", "xhat_words")
+        return [(k, t, -1) for k, t in zip(names, self.outs) if t is not None]
 
     def end_to_end(self, reps=5):
         """The whole Monte-Carlo pipeline on the device (pcub_mc_run_bin: information bits ->
@@ -272,6 +285,9 @@ class Deletion:
     def errors(self):
         return mc.error_counts(sc.unpack(self.outs[0], self.K), self.info_tx)
 
+    def outputs(self):
+        return [(k, t, -1) for k, t in zip(("info_words", "xhat_words"), self.outs) if t is not None]
+
     def bytes_alg(self):
         return float(self.rx_len.float().mean().item()) + 4 + self.N // 8 + self.K // 8
 
@@ -383,6 +399,9 @@ class Qary:
     def errors(self):
         return mc.error_counts(self.outs[0].t(), self.info_tx)
 
+    def outputs(self):
+        return [(k, t, -1) for k, t in zip(("info", "xhat"), self.outs) if t is not None]
+
     def bytes_alg(self):
         bits = max(1, (self.q - 1).bit_length())
         return 8 * self.q * self.N + (self.N * bits) // 8 + (self.K * bits) // 8
@@ -454,6 +473,14 @@ class Scl(Qary):
         sel = info.gather(0, best.view(1, 1, -1).expand(1, info.shape[1], -1))[0]  # [K, B]
         return mc.error_counts(sel.t(), self.info_tx)
 
+    def outputs(self):
+        """The list (slots past a codeword's list size hold nothing a caller reads: zeroed, so that
+        two runs compare), the path metrics and the list sizes."""
+        info, prob, size, _ = self.outs
+        live = torch.arange(self.L, device=size.device).view(-1, 1) < size.view(1, -1)  # [L, B]
+        return [("info", torch.where(live.unsqueeze(1), info, torch.zeros_like(info)), -1),
+                ("prob", torch.where(live, prob, torch.zeros_like(prob)), -1), ("size", size, -1)]
+
     def tag(self):
         return "scl_q%d_n%d_L%d" % (self.q, self.n, self.L)
 
@@ -517,6 +544,9 @@ class Stub:
         d = self.out != self.info
         return int(d.any(axis=1).sum()), int(d.sum())
 
+    def outputs(self):
+        return [("info", self.out, 0)]
+
     def bytes_alg(self):
         return 16 * self.N + self.N // 8 + self.K // 8
 
@@ -531,6 +561,36 @@ class Stub:
 
 
 WORKLOADS = {"awgn": Awgn, "deletion": Deletion, "qary": Qary, "scl": Scl, "stub": Stub}
+
+DUMP_BUDGET = 60 * 10 ** 6  # bytes of array data --dump-outputs writes at the most (64 MB less headers)
+
+
+def dump_outputs(w, directory, seed, rank, world):
+    """--dump-outputs: what the last timed step returned to its caller (w.outputs(): name, array,
+    batch axis), as <directory>/<name>.npy.  Integer words wider than a byte go out as float64
+    (exact), bytes as float32, floats as they are.  When that is more than DUMP_BUDGET bytes, the
+    same codewords of every array are kept: a sorted sample drawn from a generator seeded by
+    --seed alone, their indices in sample_index.npy."""
+    outs = []
+    for name, t, axis in w.outputs():
+        t = torch.as_tensor(t)
+        wide = t.dtype in (torch.float64, torch.int32, torch.int64)
+        outs.append((name, t, axis % t.dim(), np.float64 if wide else np.float32))
+    per_cw = sum(t.numel() // w.B * np.dtype(dt).itemsize for _, t, _, dt in outs)
+    index = None
+    if per_cw * w.B > DUMP_BUDGET:
+        keep = max(1, DUMP_BUDGET // (per_cw + 8))
+        index = np.sort(np.random.default_rng([seed, 0x0D0F]).choice(w.B, size=keep, replace=False))
+    os.makedirs(directory, exist_ok=True)
+    suffix = "" if world == 1 else ".rank%d" % rank
+    for name, t, axis, dt in outs:
+        if index is not None:
+            t = t.index_select(axis, torch.from_numpy(index).to(t.device))
+        np.save(os.path.join(directory, name + suffix + ".npy"), t.cpu().numpy().astype(dt))
+    if index is not None:
+        np.save(os.path.join(directory, "sample_index" + suffix + ".npy"), index.astype(np.float64))
+    log("rank %d: outputs of the last step written to %s (%s)" % (
+        rank, directory, "all %d codewords" % w.B if index is None else "%d of %d codewords" % (len(index), w.B)))
 
 
 def _free_port():
@@ -584,6 +644,12 @@ def build_parser():
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port when launching ranks (0 = free port)")
     ap.add_argument("--static-tiles", action="store_true",
                     help="decode kernels stride over their tiles statically instead of taking them from a counter (A/B)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the end-to-end Monte-Carlo line "
+                         "(--no-e2e leaves it out) and the CPU baseline (--no-cpu leaves it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, a fixed "
+                         "seeded sample of the codewords when the whole is more than 64 MB)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-xhat", action="store_true")
     ap.add_argument("--no-tile", action="store_true", help="awgn: root rows [N][B][2] instead of the kernel's tiles")
@@ -598,6 +664,8 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     ap = build_parser()
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world, rank, local = mc.dist_env()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -673,13 +741,16 @@ def main(argv=None):
     elapsed = time.perf_counter() - t_start
     kern_ms = [x.elapsed_time(y) for x, y in evs] if evs else [t_local * 1e3 / max(1, a.steps)]
 
+    if a.dump_outputs:
+        dump_outputs(w, a.dump_outputs, a.seed, rank, world)
+
     fe, be = w.errors()  # of the last decode (identical every step)
     counters, elapsed = mc.reduce_counters([w.B, fe, be, 0], elapsed, coll_dev)
     per_rank = mc.gather_floats([t_local, float(np.mean(kern_ms)), w.B], coll_dev)
     total_cw = counters[0] * a.steps
     value = total_cw / elapsed
     e2e = None
-    if hasattr(w, "end_to_end") and not a.no_e2e:
+    if a.full and hasattr(w, "end_to_end") and not a.no_e2e:
         if world > 1:
             dist.barrier()
         _, e2e_s = mc.reduce_counters([0], w.end_to_end(), coll_dev)
@@ -725,7 +796,7 @@ def main(argv=None):
                                             "all on device, same codewords; chunks of %d back to back, median of "
                                             "%d warm runs" % (min(w.B, a.e2e_chunk), len(w.e2e_times)),
                                     "min": e2e_spread[0], "max": e2e_spread[1]}
-        if world == 1 and not a.no_cpu and hasattr(w, "cpu_baseline"):
+        if a.full and world == 1 and not a.no_cpu and hasattr(w, "cpu_baseline"):
             rec["cpu_baseline"] = w.cpu_baseline()
         print(json.dumps(rec), flush=True)
     if world > 1:

@@ -32,6 +32,9 @@ SOURCES = ["sc_del_w4.hip", "sc_del_dense.hip", "sc_del_n4w.hip", "sc_del_n4.hip
            "sc_qary_q2.hip", "sc_qary_q3.hip", "sc_qary_q4.hip", "sc_qary_q56.hip", "sc_qary_q78.hip",
            "sc_util.hip", "sc_del.hip", "sc_leaf.hip", "sc_qary_log.hip", "scl.hip",
            "sc_mc.hip"]
+# compile order only (the link order is SOURCES'): the units that take minutes each, longest first
+SLOWEST_FIRST = ["sc_bin_k9.hip", "sc_bin_k6.hip", "sc_qary_q4.hip", "sc_qary_q78.hip", "sc_bin_k8.hip",
+                 "sc_qary_q56.hip", "sc_bin_k7.hip", "sc_del_n4o.hip", "sc_del_n4x.hip", "sc_qary_q3.hip"]
 CFLAGS = ["--offload-arch=" + ARCH, "-O3", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-std=c++17", "-Wall",
           "-Wno-unused-function"]
 
@@ -40,6 +43,16 @@ HOST_LIB = os.path.join(LIBDIR, "libpolarcub_construct.so")
 HOST_SOURCES = [os.path.join(CSRC, "host", "tv_construct.cpp"), os.path.join(CSRC, "host", "qary_construct.cpp")]
 CXX = os.environ.get("CXX", "g++")
 HOST_CFLAGS = ["-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-std=c++17", "-Wall", "-pthread"]
+
+
+def jobs():
+    """Parallel compile jobs: $MAX_JOBS, else the cores this process may run on, 16 at the most."""
+    if os.environ.get("MAX_JOBS"):
+        return max(1, int(os.environ["MAX_JOBS"]))
+    try:
+        return max(1, min(16, len(os.sched_getaffinity(0))))
+    except AttributeError:
+        return max(1, min(16, os.cpu_count() or 1))
 
 
 def _digest(paths, extra=()):
@@ -218,7 +231,10 @@ def _build_hip_locked(force, verbose):
         return LIB
     os.makedirs(OBJDIR, exist_ok=True)
     todo = [s for s in SOURCES if force or _stale(_obj(s), _obj_digest(s))]
-    with ThreadPoolExecutor(max(1, min(len(todo), int(os.environ.get("MAX_JOBS", "8"))))) as ex:
+    # the slowest translation units first: one of them alone takes longer than the rest of a
+    # worker's share, so started last it would run on with every other worker idle
+    todo.sort(key=lambda s: SLOWEST_FIRST.index(s) if s in SLOWEST_FIRST else len(SLOWEST_FIRST))
+    with ThreadPoolExecutor(max(1, min(len(todo), jobs()))) as ex:
         list(ex.map(lambda s: _compile(s, verbose), todo))
     lib_dig = _lib_digest()
     tmp = LIB + ".tmp"

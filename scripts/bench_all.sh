@@ -6,6 +6,8 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out
 python -c "import __graft_entry__ as g; g.build()" > gpurun_out/build.log 2>&1 || { echo BUILD FAILED; exit 1; }
+# the bench lines here carry the end-to-end and CPU-baseline legs, which bench.py runs only with --full
+BENCH_EXTRA="--full ${BENCH_EXTRA:-}"
 for spec in ${SPECS:-"awgn:" "deletion:" "qary:" "awgn12:--n 12"}; do
   name=${spec%%:*}; extra=${spec#*:}
   wl=${name%12}

@@ -7,6 +7,8 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out
 BATCH=${BATCH:-1048576}
+# the bench line here carries the end-to-end and CPU-baseline legs, which bench.py runs only with --full
+BENCH_EXTRA="--full ${BENCH_EXTRA:-}"
 # the library is built here (in-tree) before the call; its objects do not travel (.gpurunignore)
 if [ -z "${NO_TEST:-}" ]; then
   timeout -k 10 ${T_SMOKE:-300} python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1

@@ -41,6 +41,27 @@ def test_launcher_counters_equal_single_process(world):
     assert multi["value"] > 0 and all(p["value"] > 0 for p in multi["per_rank"])
 
 
+def test_dump_outputs_repeat_and_steps_are_honoured(tmp_path):
+    """--dump-outputs writes the last timed step's decisions as float .npy files, the same from run
+    to run with the same arguments (whatever --steps, --warmup and --full are); --steps sets the
+    timed steps, and the line carries ms_per_step; a plain run has none of --full's legs."""
+    import numpy as np
+    B = 40
+    common = ["--gpus", "1", "--workload", "stub", "--batch", str(B)]
+    one = _bench(*common, "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "a"))
+    two = _bench(*common, "--steps", "1", "--warmup", "0", "--full", "--dump-outputs", str(tmp_path / "b"))
+    assert one["steps"] == 3 and two["steps"] == 1
+    for rec in (one, two):
+        assert rec["ms_per_step"] > 0
+        assert abs(rec["value"] - rec["codewords_per_step"] / (rec["ms_per_step"] / 1e3)) <= 1e-6 * rec["value"]
+    assert "cpu_baseline" not in one and "mc_end_to_end" not in one
+    a, b = np.load(tmp_path / "a" / "info.npy"), np.load(tmp_path / "b" / "info.npy")
+    assert a.dtype in (np.float32, np.float64) and a.shape == (B, 32)
+    assert np.array_equal(a, b) and set(np.unique(a)) <= {0.0, 1.0}
+    assert int((a.sum(axis=1) > 0).sum()) > 0  # decisions, not an empty buffer
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["info.npy"]
+
+
 def test_rank_offsets_tile_the_global_batch():
     B = 1 << 20
     offs = [mc.rank_offset(r, B) for r in range(8)]
