@@ -114,9 +114,9 @@ int pcub_polar_encode_bin(const uint32_t* info_words, int64_t B, int32_t log2N, 
  * (VectorDistributions/CollectionOfBinaryTrellises.py:106-129, BinaryTrellis.py:309-438,
  * Guardbands.py:47-93) builds from each received word.
  *   rx          [B][stride] u8 received symbols (0/1), rx_len[b] <= stride of them valid
- *   n, n0       code length 2^n, 2^n0 inputs per trellis; supported (decode):
- *               1 <= n0 <= 4, 1 <= n - n0 <= 8 (decode and leaf export), and n0 = 4 with
- *               n - n0 = 9, 10 without ones (decode; main_deletion's n = 13, 14)
+ *   n, n0       code length 2^n, 2^n0 inputs per trellis; supported (decode and leaf export
+ *               alike): 1 <= n0 <= 4, 1 <= n - n0 <= 8, and n0 = 4 with n - n0 = 9, 10
+ *               without ones (main_deletion's n = 13, 14)
  *               (pcub_sc_deletion_supported / pcub_sc_leaf_deletion_supported)
  *   ones        numberOfOnesToAddAtBothEndsOfGuardbands, 0 <= ones <= 3
  *   pd          deletion probability the trellises are built with

@@ -525,15 +525,30 @@ def _device_genie_bin(length, xy, U):
     return m.cpu().numpy()
 
 
+# Device bytes one _device_genie_deletion call may hold in leaves and marginals: a genie chunk of
+# 4096 trials at N = 16384 would otherwise ask for 2 GiB at once.
+_GENIE_DEVICE_BYTES = 1 << 30
+
+
 def _device_genie_deletion(length, shape, words, U):
+    """Genie decodes of deletion-channel trials on the GPU: all positions frozen to the trial's u.
+    Returns leaf marginals [T, N, 2] (numpy), in trial order.  The trials go to the device in
+    sub-batches whose leaves [N, b], transposed leaves and marginals [b, N, 2] (32 N bytes a trial)
+    stay under _GENIE_DEVICE_BYTES; a trial's leaves do not depend on its batch."""
     import torch
 
     from . import sc
     pd, n, n0, ones = shape
     code = sc.CodeSpec(length, np.ones(length, np.uint8), np.zeros(length, np.uint8))
-    rx, ln = sc.pad_words(words, code.device)
-    _, _, m = sc.DeletionDecoder(code, n0, pd, ones).decode_leaves(rx, ln, torch.from_numpy(U).to(code.device))
-    return m.cpu().numpy()
+    dec = sc.DeletionDecoder(code, n0, pd, ones)
+    step = max(1, _GENIE_DEVICE_BYTES // (32 * length))
+    out = np.empty((len(words), length, 2), np.float64)
+    for b0 in range(0, len(words), step):
+        rx, ln = sc.pad_words(words[b0:b0 + step], code.device)
+        m = dec.decode_leaves(rx, ln, torch.from_numpy(U[b0:b0 + step]).to(code.device))[2]
+        out[b0:b0 + step] = m.cpu().numpy()
+        del m
+    return out
 
 
 def write_frozen_file(filename, frozenSet, numberOfTrials, TVvec, Pevec, argv=None):

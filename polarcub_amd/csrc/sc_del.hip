@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256) void k_del_n02_table(double pd, double* tab) {
 DelKern del_kernel(int n0, int tb, bool exp, int ones) {
     if (ones < 0 || ones > kMaxOnes) return nullptr;
     const int oc = ones > 0 ? kMaxOnes : 0;
-    if (tb > 8) return n0 == 4 && !exp && oc == 0 ? del_kernel_n4_wide(tb) : nullptr;
+    if (tb > 8) return n0 == 4 && oc == 0 ? (exp ? del_kernel_n4_wide_x(tb) : del_kernel_n4_wide(tb)) : nullptr;
 #define PCUB_DEL_PICK(k) \
     case k: return exp ? del_kernel_n##k##_x(tb, oc) : oc == 0 ? del_kernel_n##k##_d0(tb) : del_kernel_n##k##_d3(tb);
     switch (n0) {

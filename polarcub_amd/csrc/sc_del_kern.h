@@ -288,10 +288,12 @@ struct DelCtx {
     // at leaf[u * B] by the leader (BinaryPolarEncoderDecoder.py:268-273).  Values keep the
     // half-split order of XSub: a node of length M at positions [0, M) has children
     // op(v[p], v[p + M/2]) at [0, M/2), and its encoding is [ym ^ yp | yp].  The genie path,
-    // not the throughput path: ~3 barriers per leaf.
+    // not the throughput path: ~6 barriers per leaf (2 at the decision, 1 a level walked).  At T = 512 / 1024 the codeword is the
+    // whole workgroup (8 / 16 waves): every barrier below sits under conditions on i and d
+    // alone, never on p, the leader or a frozen bit, so all T threads reach each of them.
     __device__ __forceinline__ uint32_t export_wide(double v, uint64_t* ub, const uint64_t* fm, const uint64_t* fv) {
-        constexpr int m = T == 128 ? 7 : 8;
-        static_assert(T == 128 || T == 256, "wide export: 128 or 256 trellises");
+        constexpr int m = __builtin_ctz((unsigned)T);  // log2 T: the node's SC depth
+        static_assert(T == 128 || T == 256 || T == 512 || T == 1024, "wide export: 128 .. 1024 trellises");
         const int p = threadIdx.x & (T - 1);
         const int g = threadIdx.x / T;
         double* V = xe + g * 2 * T;
@@ -660,8 +662,8 @@ __device__ __forceinline__ void del_group(const DelArgs& A, long long grp, uint3
     __shared__ double xv[(T >= 64 && !EXP) ? BLK : 1];
     __shared__ unsigned long long xb[(T >= 64 && !EXP) ? DelCtx<T, EXP>::LV : 1],
         xub[(T >= 64 && !EXP) ? CPB * DelCtx<T, EXP>::NW : 1];
-    __shared__ double xe[(T > 64 && EXP) ? 2 * kDelBlock : 1];
-    __shared__ uint8_t xeb[(T > 64 && EXP) ? 2 * kDelBlock : 1];
+    __shared__ double xe[(T > 64 && EXP) ? CPB * 2 * T : 1];  // = 2 * BLK: 16 KB + 2 KB at T = 1024
+    __shared__ uint8_t xeb[(T > 64 && EXP) ? CPB * 2 * T : 1];
     DelCtx<T, EXP> cx;
     cx.xe = xe;
     cx.xeb = xeb;
@@ -720,7 +722,6 @@ __global__ __launch_bounds__(del_block<(1 << TB)>()) void k_sc_del(DelArgs A) {
     constexpr int CPB = BLK / T;                      // codewords per workgroup
     constexpr int WPC = ((T << N0) + 31) / 32;        // x_hat words per codeword
     static_assert(T <= 1024, "at most one workgroup per codeword");
-    static_assert(!EXP || T <= kDelBlock, "export mode: at most 256 trellises");
     constexpr bool TAB = N0 == 2 && OC == 0;  // the n0 = 2 stage through the state table
     __shared__ uint32_t xs[CPB * WPC];
     __shared__ double n02tab[TAB ? kN02States * kN02Row : 1];
@@ -753,8 +754,9 @@ PCUB_DEL_TABLE(3)
 PCUB_DEL_TABLE(4)
 #undef PCUB_DEL_TABLE
 // 512 and 1024 trellises of 2^4 inputs (a workgroup of T threads per codeword; main_deletion's
-// n0 = n // 3 at n = 13, 14), decode without ones: sc_del_n4w.hip
+// n0 = n // 3 at n = 13, 14), decode without ones: sc_del_n4w.hip; their export twins: sc_del_n4wx.hip
 DelKern del_kernel_n4_wide(int tb);
+DelKern del_kernel_n4_wide_x(int tb);
 // 16-input trellises (n0 = 4) without ones, 64 .. 1024 trellises, decode: one wave a (trellis,
 // depth-3 node) task, the trellises in LDS (trellis_wave.h): sc_del_w4.hip
 DelKern del_kernel_w4(int tb, int alt = 0);

@@ -681,7 +681,8 @@ def deletion_supported(n, n0, ones=0):
 
 
 def leaf_deletion_supported(n, n0, ones=0):
-    """True when pcub_sc_leaf_deletion (every leaf exported: the genie) covers the shape."""
+    """True when pcub_sc_leaf_deletion (every leaf exported: the genie) covers the shape: every shape
+    deletion_supported accepts, the 512 / 1024-trellis shapes of n0 = 4 (n = 13, 14) included."""
     return bool(_lib.lib().pcub_sc_leaf_deletion_supported(int(n), int(n0), int(ones)))
 
 
@@ -803,7 +804,10 @@ class DeletionDecoder:
         return unpack(info_w, self.code.K), unpack(xh_w, self.code.N)
 
     def decode_leaves(self, rx, rx_len, fval_cw=None):
-        """Export mode (pcub_sc_leaf_deletion): (info [B, K], xhat [B, N], marginals [B, N, 2])."""
+        """Export mode (pcub_sc_leaf_deletion): (info [B, K], xhat [B, N], marginals [B, N, 2]).
+        Covers every shape decode() does (up to 1024 trellises a codeword at n0 = 4).  Device memory
+        is 32 N bytes a codeword (leaves, their transpose, marginals): callers with thousands of long
+        codewords split the batch (coding._device_genie_deletion)."""
         c = self.code
         if not leaf_deletion_supported(c.n, self.n0, self.ones):
             raise ValueError("no leaf-export deletion kernel for n=%d, n0=%d, ones=%d" % (c.n, self.n0, self.ones))
