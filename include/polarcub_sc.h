@@ -116,7 +116,10 @@ int pcub_polar_encode_bin(const uint32_t* info_words, int64_t B, int32_t log2N, 
  *   rx          [B][stride] u8 received symbols (0/1), rx_len[b] <= stride of them valid
  *   n, n0       code length 2^n, 2^n0 inputs per trellis; supported (decode and leaf export
  *               alike): 1 <= n0 <= 4, 1 <= n - n0 <= 8, and n0 = 4 with n - n0 = 9, 10
- *               without ones (main_deletion's n = 13, 14)
+ *               without ones (main_deletion's n = 13, 14); decode only (no leaf export): n0 = 5
+ *               with 6 <= n - n0 <= 10 without ones (n = 11 .. 15; main_deletion's n = 15), where
+ *               a row of more than 8 * 116,592 symbols (8 * 155,456 up to n = 12) is PCUB_EINVAL
+ *               and `table` is ignored.  Not covered: n0 = 5 with ones, n - n0 < 6, n >= 16
  *               (pcub_sc_deletion_supported / pcub_sc_leaf_deletion_supported)
  *   ones        numberOfOnesToAddAtBothEndsOfGuardbands, 0 <= ones <= 3
  *   pd          deletion probability the trellises are built with

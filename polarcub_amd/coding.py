@@ -223,9 +223,14 @@ class BinaryPolarEncoderDecoder:
             return (enc[0], info[0])
         shape = _deletion_kernel_shape(xyVectorDistribution)
         if shape is not None and _is_uniform_prior(xVectorDistribution):
-            enc, info = self.decode_deletion_batch([xyVectorDistribution.deletion_source[0]], shape[0], shape[2],
-                                                   shape[3])
-            return (enc[0], info[0])
+            try:
+                enc, info = self.decode_deletion_batch([xyVectorDistribution.deletion_source[0]], shape[0], shape[2],
+                                                       shape[3])
+                return (enc[0], info[0])
+            except ValueError:
+                # the launcher refused the row (PCUB_EINVAL: too long for the kernel's LDS, n0 = 5): the
+                # recursion over the host trellises below decodes it
+                pass
         prior = _prior_rows(xVectorDistribution, self.length)
         if prior is not None and _is_memoryless_binary(xyVectorDistribution):
             enc, info = self.decode_prior_batch(prior, _check_joint(xyVectorDistribution.probs)[None, :, :])
@@ -381,10 +386,16 @@ def encodeDecodeSimulation(length, make_xVectorDistribution, make_codeword, simu
         elif batch_xy:
             results["bin"] = encDec.decode_prior_batch(prior, np.stack(batch_xy))[1]
         for shape, words in batch_del.items():
-            results[shape] = encDec.decode_deletion_batch(words, shape[0], shape[2], shape[3])[1]
+            try:
+                results[shape] = encDec.decode_deletion_batch(words, shape[0], shape[2], shape[3])[1]
+            except ValueError:
+                results[shape] = None  # a row the launcher refused (too long): word by word below
         for (t, codeword, received, info_t) in pending:
             if isinstance(info_t, tuple):
-                info_t = results[info_t[0]][info_t[1]]
+                if results[info_t[0]] is None:
+                    info_t = encDec.decode(xvd, make_xyVectrorDistribution(received))[1]
+                else:
+                    info_t = results[info_t[0]][info_t[1]]
             if np.any(info_t != infos[t]):
                 errors += 1
                 if verbosity > 0:

@@ -25,6 +25,11 @@ extern "C" int pcub_sc_dynamic_tiles(void);  // sc_bin.hip: work tiles from a co
 
 namespace pcub {
 int del_w4_block(int tb);  // sc_del_w4.hip: threads a workgroup of del_kernel_w4(tb)
+// 32-input trellises (n0 = 5) without ones, 64 .. 1024 trellises, decode: one wave a (trellis,
+// depth-4 node) task (trellis_wave5.h): sc_del_w5.hip
+DelKern del_kernel_w5(int tb);
+int del_w5_block(int tb);  // threads a workgroup of del_kernel_w5(tb)
+long long del_w5_rx_bytes(int tb);  // the longest packed received row it takes (it lies in the kernel's own LDS)
 }
 
 namespace {
@@ -144,6 +149,10 @@ DelKern del_kernel(int n0, int tb, bool exp, int ones) {
 #undef PCUB_DEL_PICK
 }
 
+// n0 = 5 is served by the wave-per-task kernel alone (sc_del_w5.hip): decode without ones, 64 .. 1024
+// trellises (n = 11 .. 15); no export, no lane-per-trellis twin
+bool w5_shape(int n0, int tb, int ones) { return n0 == 5 && ones == 0 && tb >= 6 && tb <= 10; }
+
 // comb(ones, i) * (1 - pd)^i * pd^(ones - i), left to right as the reference evaluates it
 // (BinaryTrellis.py:343-345), with libm pow like CPython's float ** int.
 OnesProbs ones_probs(int ones, double pd) {
@@ -194,7 +203,8 @@ int launch_del(bool exp, const uint8_t* rx, const int32_t* rx_len, int64_t B, in
                int32_t ones, double pd, const uint32_t* frozen_mask, const uint32_t* frozen_val,
                const uint32_t* frozen_val_cw, int32_t K, uint32_t* info_words, uint32_t* xhat_words, double* leaf,
                const double* table, void* stream) {
-    const DelKern kern = del_kernel(n0, n - n0, exp, ones);
+    const bool w5 = !exp && w5_shape(n0, n - n0, ones);
+    const DelKern kern = w5 ? del_kernel_w5(n - n0) : del_kernel(n0, n - n0, exp, ones);
     if (!kern || B < 0 || stride < 0 || stride > kMaxStride || !frozen_mask || (!frozen_val && !frozen_val_cw))
         return PCUB_EINVAL;
     if (K < 0 || K > (1 << n) || (!exp && K > 0 && !info_words) || (B > 0 && (!rx || !rx_len))) return PCUB_EINVAL;
@@ -219,6 +229,31 @@ int launch_del(bool exp, const uint8_t* rx, const int32_t* rx_len, int64_t B, in
     A.gate = nullptr;
     A.gate_id = 0;
     const long long rw = ((long long)stride + 31) / 32;
+    // n0 = 5 without ones (main_deletion's n = 15): one wave a (trellis, depth-4 node) task, the
+    // trellises in LDS (sc_del_w5.hip), codewords from a per-launch counter; no workspace
+    if (w5) {
+        // the kernel parses the packed row out of its task waves' LDS buffers: a row too long for them is
+        // refused here, before any launch
+        if (rw * 4 > del_w5_rx_bytes(n - n0)) return PCUB_EINVAL;
+        const int wblk = del_w5_block(n - n0);
+        const size_t lds = 0;
+        int occ = 0, dev = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, wblk, lds) != hipSuccess || occ <= 0)
+            return PCUB_EINVAL;
+        long long grid = B;
+        if (hipGetDevice(&dev) == hipSuccess &&
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0 &&
+            grid > (long long)cus * occ)
+            grid = (long long)cus * occ;
+        A.rw = (int)rw;
+        A.tab = nullptr;
+        if (pcub_sc_dynamic_tiles()) {
+            const int rc = counter_slot(&A.wtiles, (hipStream_t)stream);
+            if (rc) return rc;
+        }
+        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(wblk), lds, (hipStream_t)stream, A);
+        return (int)hipGetLastError();
+    }
     // n0 = 4 without ones (main_deletion's n = 12 .. 14): one wave a (trellis, depth-3 node) task, the
     // trellises in LDS (sc_del_w4.hip), codewords from a per-launch counter
     const int w4m = g_wave4.load(std::memory_order_relaxed);
@@ -316,7 +351,7 @@ int launch_del(bool exp, const uint8_t* rx, const int32_t* rx_len, int64_t B, in
 }  // namespace
 
 extern "C" int pcub_sc_deletion_supported(int32_t n, int32_t n0, int32_t ones) {
-    return del_kernel(n0, n - n0, false, ones) != nullptr;
+    return del_kernel(n0, n - n0, false, ones) != nullptr || w5_shape(n0, n - n0, ones);
 }
 
 extern "C" int pcub_sc_leaf_deletion_supported(int32_t n, int32_t n0, int32_t ones) {
