@@ -1570,6 +1570,113 @@ def fx_edge_long(R, timing):
 FIXTURES["edge_long"] = fx_edge_long
 
 
+# ---------------------------------------------------------------------------
+# the shapes the wave-per-task deletion kernels serve (n0 = 4 at n >= 10, n0 = 5)
+# ---------------------------------------------------------------------------
+
+def ref_deletion_words(R, n, n0, pds, xi, ones, frozen, crs, info_seed, channel_seed):
+    """Received words only: the reference's encode -> guard bands -> deletionChannelSimulation, word t at
+    deletion rate pds[t].  The information of word t is the one ref_deletion_trials draws for its
+    word t from the same info_seed, so a later rx_override run keeps tx_info aligned with the words."""
+    BPED = R["BPED"]
+    make_x, make_codeword, _, _ = deletion_closures(R, n, n0, pds[0], xi, ones, channel_seed)
+    channels = {pd: deletion_closures(R, n, n0, pd, xi, ones, channel_seed + k)[2]
+                for k, pd in enumerate(sorted(set(pds)))}
+    xvd = make_x()
+    enc = BPED.BinaryPolarEncoderDecoder(1 << n, frozen, crs)
+    irng = random.Random()
+    irng.seed(info_seed)
+    words = []
+    for pd in pds:
+        inf = [0 if irng.random() < 0.5 else 1 for _ in range(enc.k)]
+        cw = make_codeword(enc.encode(xvd, inf))
+        words.append([int(b) for b in channels[pd](cw)])
+    return words, len(cw)
+
+
+# (n, n0, pd, words in total, words whose leaf marginals are stored, frozen set).  Frozen set "half":
+# rate about 1/2 at random; at that rate the reference's decode of a channel word goes wrong early and
+# most of its later leaves are ties, so each shape of a kernel also has a "low" case: rate 1/16 on the
+# positions of largest index weight (the Reed-Muller rule), which the reference decodes correctly, every
+# leaf live to the end.
+DELETION_WAVE_CASES = [(6, 5, 0.1, 8, 8, "half"), (6, 5, 0.25, 8, 8, "half"), (7, 5, 0.1, 8, 8, "half"),
+                       (7, 5, 0.25, 8, 8, "half"), (10, 4, 0.1, 8, 8, "half"), (11, 5, 0.1, 8, 8, "half"),
+                       (12, 4, 0.25, 8, 2, "half"), (13, 4, 0.1, 5, 2, "half"), (14, 4, 0.1, 4, 0, "half"),
+                       (13, 5, 0.2, 4, 0, "half"), (15, 5, 0.1, 3, 0, "half"),
+                       (10, 4, 0.05, 8, 8, "low"), (11, 5, 0.05, 8, 4, "low"), (12, 4, 0.1, 5, 1, "low"),
+                       (13, 4, 0.05, 4, 1, "low"), (14, 4, 0.05, 3, 0, "low"), (13, 5, 0.1, 3, 0, "low"),
+                       (15, 5, 0.05, 3, 0, "low")]
+
+
+def fx_deletion_wave(R, timing):
+    """The shapes of the wave-per-task deletion kernels (16-input trellises at n = 10, 12, 13, 14 and
+    32-input trellises at n = 6, 7, 11, 13, 15; ones = 0, xi = 0.1): channel words at the case's pd, one
+    channel word drawn at pd 0.4 (segments from empty to overlong), the empty word, an all-zero word
+    of half the codeword length and a random word 1.5 x the codeword length (every segment past
+    2^n0), each decoded by the reference at the case's pd.  Frozen sets: the first quarter frozen
+    (rate-0 nodes down to depth 2), then a third of the rest at random, so the rate is about 1/2
+    ("half"), or all but the N / 16 positions of largest index weight ("low", see
+    DELETION_WAVE_CASES); crs >= 0, so the frozen values are mixed."""
+    import trellis_oracle as tro
+    rng = np.random.default_rng(4511)
+    out = {}
+    for ci, (n, n0, pd, T, nleaf, kind) in enumerate(DELETION_WAVE_CASES):
+        N = 1 << n
+        mask = rng.random(N) < 1.0 / 3.0
+        if kind == "low":
+            mask[:] = True
+            mask[sorted(range(N // 4, N), key=lambda i: (bin(i).count("1"), i))[-(N // 16):]] = False
+        mask[: N // 4] = True
+        frozen = set(int(i) for i in np.nonzero(mask)[0])
+        crs = int(rng.integers(0, 500))
+        info_seed, channel_seed = int(rng.integers(1, 999)), int(rng.integers(1, 999))
+        # 8 words: 4 at pd, 1 at 0.4, empty, zeros, overlong; 5: 2, 1, empty, overlong;
+        # 4: 1, 1, empty, overlong; 3: 1 at pd, empty, overlong
+        nch = {8: 5, 5: 3, 4: 2, 3: 1}[T]
+        pds = [pd] * (nch - 1) + [0.4] if nch > 1 else [pd]
+        t0 = time.perf_counter()
+        words, cwl = ref_deletion_words(R, n, n0, pds, 0.1, 0, frozen, crs, info_seed, channel_seed)
+        words.append([])
+        if T == 8:
+            words.append([0] * (cwl // 2))
+        words.append([int(b) for b in rng.integers(0, 2, cwl + cwl // 2)])
+        assert len(words) == T
+        d, _ = ref_deletion_trials(R, n, n0, pd, 0.1, 0, frozen, crs, info_seed, channel_seed, T, rx_override=words)
+        dt = (time.perf_counter() - t0) / T
+        timing["deletion_wave_n%d_n0%d_pd%g_s_per_cw" % (n, n0, pd)] = dt
+        # conditions that keep the case from being vacuous
+        K = d["info"].shape[1]
+        assert K > 0, (n, n0)
+        assert any(not np.array_equal(d["info"][t], d["info"][u]) for t in range(nch) for u in range(T)), (n, n0)
+        seglens = set(len(s) for w in words for s in tro.remove_guard_bands(w, n, n0))
+        if kind == "low":  # a live decode: a channel word at the case's pd is decoded correctly
+            assert any(np.array_equal(d["info"][t], d["tx_info"][t]) for t in range(max(1, nch - 1))), (n, n0)
+        if T >= 5:
+            assert 0 in seglens and any(1 <= l <= 1 << n0 for l in seglens) and max(seglens) > 1 << n0, (n, n0)
+        print("  (%d, %d) pd %g %s: K %d, %d words, %.1f s a word, segment lengths %d..%d, words decoded correctly %s"
+              % (n, n0, pd, kind, K, T, dt, min(seglens), max(seglens),
+                 [t for t in range(T) if np.array_equal(d["info"][t], d["tx_info"][t])]))
+        d.pop("cw_len")
+        d.pop("r")  # N doubles a case: fval is what the decoders take, and crs regenerates r
+        d["crs"] = np.array([crs], np.int32)
+        # the marginals at the information leaves only (what the tests compare), first words only
+        d["leaf_mi"] = np.ascontiguousarray(d.pop("leaf_m")[:nleaf][:, d["frozen"] == 0])
+        for k, v in d.items():
+            out["c%d_%s" % (ci, k)] = v
+        out["c%d_shape" % ci] = np.array([n, n0, 0, nch, kind == "low"], np.int32)
+        out["c%d_pd" % ci] = np.array([pd])
+    save("deletion_wave", dict(cases=len(DELETION_WAVE_CASES), xi=0.1,
+                               note="shape = (n, n0, ones, channel words, low-rate frozen set); the last channel word of a case "
+                                    "with two or more is drawn at pd 0.4; then the empty word, (8-word cases) "
+                                    "zeros of half the codeword length, a random word 1.5 x the codeword "
+                                    "length; leaf_mi holds the marginals at the information leaves of the first words"), **out)
+    size = os.path.getsize(os.path.join(OUT, "deletion_wave.npz"))
+    assert size <= 1 << 20, "deletion_wave.npz is %d bytes: store fewer leaf_m words" % size
+
+
+FIXTURES["deletion_wave"] = fx_deletion_wave
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", nargs="*")

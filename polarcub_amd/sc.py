@@ -700,7 +700,9 @@ def set_deletion_rate1(on):
 def set_deletion_wave(on):
     """Diagnostic: 0 sends n0 = 4 deletion decodes (64 .. 1024 trellises) back to the lane-per-trellis
     kernel instead of the wave-per-task kernel (pcub_sc_set_deletion_wave, not part of the stable ABI);
-    returns the previous setting.  Decisions are identical either way."""
+    1 (the default) and 2 run the wave kernel at every one of those sizes; returns the previous setting.
+    Decisions are identical under 0, 1 and 2.  3 is a timing probe: the wave kernel with its trellis
+    tasks skipped, so its info and x_hat are NOT the decode's and must not be used."""
     import ctypes
     f = _lib.lib().pcub_sc_set_deletion_wave
     f.restype = ctypes.c_int

@@ -1,7 +1,8 @@
 """The n0 = 5 wave-per-task trellises (polarcub_amd/csrc/trellis_wave5.h) compiled for the host and run
 with their lanes one after another (tests/emu5/w5_check.cpp) against trellis_body.h's Trel walk at
-L = 32; and the C oracle against the Python oracle at n0 = 5, which the GPU tests of those shapes
-rest on."""
+L = 32; the C oracle against the Python oracle at n0 = 5, which the GPU tests of those shapes
+rest on; and the Python oracle against the reference's own decodes at n0 = 5
+(tests/golden/deletion_wave.npz; the C oracle meets them in tests/test_trellis_oracle.py)."""
 import os
 import random
 import subprocess
@@ -11,6 +12,7 @@ import pytest
 
 from oracle import trellis_oracle as tro
 from tests.conftest import ROOT
+from tests.test_trellis_oracle import _check, _words, wave_case
 
 
 def test_wave5_trellises_match_trel():
@@ -50,3 +52,16 @@ def test_c_oracle_matches_python_oracle_n05(n, n0):
     for i, w in enumerate(words):
         x, inf = tro.decode_deletion(w, n, n0, pd, frozen, fval, 0)
         assert list(info[i]) == inf and list(xhat[i]) == x, i
+
+
+@pytest.mark.parametrize("n,pd,nwords", [(6, 0.1, 8), (6, 0.25, 8), (7, 0.1, 8), (7, 0.25, 8), (11, 0.1, 8),
+                                         (11, 0.05, 4)])
+def test_python_oracle_matches_wave_fixture_n05(n, pd, nwords):
+    """oracle/trellis_oracle.py against the reference at 32-input trellises (two, four and 64 a codeword):
+    info, x_hat and the marginals at information leaves bit-exact, every word whose marginals the
+    fixture stores (channel words at the case's pd and at 0.4, the empty word, an all-zeros and an
+    overlong one; (11, 5, 0.05), the frozen set the reference decodes correctly: the channel words).
+    (13, 5) and (15, 5) are left to the C oracle: the Python restatement takes seconds a word there."""
+    c = wave_case(n, 5, pd)
+    assert c["nleaf"] == nwords
+    _check(_words(c)[:nwords], n, 5, pd, 0, c["frozen"], c["fval"], c["info"], c["xhat"], c["leaf_m"])

@@ -200,3 +200,91 @@ def test_tiled_root_layout(sc, variant):
             assert torch.equal(info, ci) and torch.equal(xh, cx), N
     finally:
         sc.set_variant()
+
+
+def _decode_bin_c(sc, code, native, ws_bytes):
+    """pcub_sc_decode_bin on [N, B, 2] rows with a workspace of exactly ws_bytes bytes."""
+    from polarcub_amd import _lib
+    B = native.shape[1]
+    info = torch.zeros((max(1, code.info_words), B), dtype=torch.int32, device="cuda")
+    xh = torch.zeros((code.n_words, B), dtype=torch.int32, device="cuda")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+    rc = _lib.lib().pcub_sc_decode_bin(sc._p(native), B, code.n, sc._p(code.fmask_dev), sc._p(code.fval_dev), code.K,
+                                       sc._p(info), sc._p(xh), None, sc._p(ws), ws.numel(), sc._stream())
+    assert rc == 0
+    torch.cuda.synchronize()
+    return sc.unpack(info, code.K), sc.unpack(xh, code.N)
+
+
+@pytest.mark.parametrize("variant,N,runs", [(26, 1024, 26), (24, 1024, 24), (26, 4096, 30), (26, 8192, 33)])
+def test_one_workgroup_decodes_every_tile(sc, variant, N, runs):
+    """A workspace sized for one codeword: the launcher clamps the grid to the one workgroup whose slots
+    fit, and that workgroup goes over every wave tile of 1,007 codewords (a ragged last tile), with the
+    tiles from the per-launch counter and on the static stride.  Both equal the oracle, bit for bit."""
+    from oracle import orc
+    from polarcub_amd import _lib
+    n = N.bit_length() - 1
+    B = 1000 + 7
+    rng = np.random.default_rng(600 + runs + n)
+    frozen = (rng.random(N) < 0.5).astype(np.uint8)
+    fval = (rng.random(N) < 0.5).astype(np.uint8)
+    xy = rng.random((B, N, 2))
+    xy[rng.random((B, N)) < 0.05] = 0.0
+    ri, rx = orc.decode_bin(xy, frozen, fval)
+    native = torch.from_numpy(np.ascontiguousarray(xy.transpose(1, 0, 2))).cuda()
+    sc.set_variant(variant)
+    old = sc.set_dynamic_tiles(1)
+    try:
+        assert sc.variant_for(n) == runs
+        code = sc.CodeSpec(N, frozen, fval)
+        one = int(_lib.lib().pcub_sc_decode_bin_workspace(1, n))
+        assert 0 < one < int(_lib.lib().pcub_sc_decode_bin_workspace(B, n))
+        outs = []
+        for dyn in (1, 0):
+            sc.set_dynamic_tiles(dyn)
+            outs.append(_decode_bin_c(sc, code, native, one))
+        assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+        assert np.array_equal(outs[0][0].cpu().numpy(), ri)
+        assert np.array_equal(outs[0][1].cpu().numpy(), rx)
+    finally:
+        sc.set_dynamic_tiles(old)
+        sc.set_variant()
+
+
+@pytest.mark.parametrize("N,runs", [(1024, 26), (4096, 30)])
+def test_full_grid_three_rounds(sc, N, runs):
+    """The shipped kernels at one workgroup a CU (set_max_blocks_per_cu(1)) on three full rounds of the
+    grid plus five codewords: every workgroup goes round its tile loop three times and a few a fourth,
+    with the tiles from the per-launch counter and on the static stride.  The batch repeats 256
+    distinct rows in a shuffled order; every copy equals the oracle's decode of its original."""
+    from oracle import orc
+    n = N.bit_length() - 1
+    rng = np.random.default_rng(700 + n)
+    frozen = (rng.random(N) < 0.5).astype(np.uint8)
+    fval = (rng.random(N) < 0.5).astype(np.uint8)
+    xy = rng.random((256, N, 2))
+    xy[rng.random((256, N)) < 0.05] = 0.0
+    ri, rx = orc.decode_bin(xy, frozen, fval)
+    sc.set_variant()
+    assert sc.variant_for(n) == runs
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    B = 3 * cus * sc.bin_tile(n) * 4 + 5
+    order = np.concatenate([rng.permutation(256) for _ in range(B // 256 + 1)])[:B]
+    idx = torch.from_numpy(order).cuda()
+    native = torch.from_numpy(np.ascontiguousarray(xy.transpose(1, 0, 2))).cuda().index_select(1, idx)
+    want_i = torch.from_numpy(ri).cuda().index_select(0, idx)
+    want_x = torch.from_numpy(rx).cuda().index_select(0, idx)
+    code = sc.CodeSpec(N, frozen, fval)
+    dec = sc.BinaryDecoder(code)
+    old = sc.set_dynamic_tiles(1)
+    sc.set_max_blocks_per_cu(1)
+    try:
+        for dyn in (1, 0):
+            sc.set_dynamic_tiles(dyn)
+            info_w, xh_w, _ = dec.decode_native(native)
+            torch.cuda.synchronize()
+            assert torch.equal(sc.unpack(info_w, code.K), want_i), dyn
+            assert torch.equal(sc.unpack(xh_w, code.N), want_x), dyn
+    finally:
+        sc.set_max_blocks_per_cu(0)
+        sc.set_dynamic_tiles(old)

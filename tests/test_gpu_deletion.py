@@ -10,7 +10,7 @@ import torch
 
 from oracle import trellis_oracle as tro
 from tests.conftest import load_golden
-from tests.test_trellis_oracle import deletion_edge_cases
+from tests.test_trellis_oracle import deletion_edge_cases, wave_case
 
 pytestmark = pytest.mark.gpu
 
@@ -159,10 +159,150 @@ def test_wave_kernel_matches_lane_kernel(sc, n):
             sc.set_deletion_wave(old)
         assert np.array_equal(info_w, info_l), (n, fs)
         assert np.array_equal(xhat_w, xhat_l), (n, fs)
-        if n <= 12:
-            i_ref, x_ref = orc.decode_deletion(rx, ln, n, n0, pd, frozen, fval)
-            assert np.array_equal(info_w, i_ref), (n, fs)
-            assert np.array_equal(xhat_w, x_ref), (n, fs)
+        i_ref, x_ref = orc.decode_deletion(rx, ln, n, n0, pd, frozen, fval)
+        assert np.array_equal(info_w, i_ref), (n, fs)
+        assert np.array_equal(xhat_w, x_ref), (n, fs)
+
+
+@pytest.mark.parametrize("n,pd", [(10, 0.1), (12, 0.25), (13, 0.1), (14, 0.1), (10, 0.05), (12, 0.1), (13, 0.05),
+                                  (14, 0.05)])
+def test_wave_fixture_every_dispatch(sc, n, pd):
+    """n0 = 4 at 64, 256, 512 and 1024 trellises against the reference's own decodes
+    (tests/golden/deletion_wave.npz: channel words, one at pd 0.4, the empty word, an all-zeros and an
+    overlong one; the first quarter frozen, so rate-0 depth-3 nodes; at rate 1/2, and at the rate 1/16
+    at which the reference decodes correctly and every leaf is live): the dispatch as shipped, the wave
+    kernel forced and the lane kernel, info and x_hat bit-exact each way."""
+    c = wave_case(n, 4, pd)
+    assert sc.deletion_supported(n, 4, 0)
+    outs = {"default": _dec(sc, n, 4, c["pd"], c["frozen"], c["fval"], c["rx"].copy(), c["rx_len"].copy())}
+    old = sc.set_deletion_wave(2)
+    try:
+        outs["wave"] = _dec(sc, n, 4, c["pd"], c["frozen"], c["fval"], c["rx"].copy(), c["rx_len"].copy())
+        sc.set_deletion_wave(0)
+        outs["lane"] = _dec(sc, n, 4, c["pd"], c["frozen"], c["fval"], c["rx"].copy(), c["rx_len"].copy())
+    finally:
+        sc.set_deletion_wave(old)
+    for name, (info, xhat) in outs.items():
+        assert np.array_equal(info, c["info"]), (n, name)
+        assert np.array_equal(xhat, c["xhat"]), (n, name)
+
+
+def _w4_loop_words(n):
+    """The distinct words of test_w4_persistent_loop: channel words at pd 0.02 .. 0.45, the empty word, a
+    one-symbol word, a short random and an overlong random one; a frozen set whose depth-3 nodes 0, 1
+    and 4 are rate-0 (tasks skipped: the cached depth-1 / depth-2 trellises are reloaded, rebuilt and
+    skipped within one codeword); and the C oracle's decodes."""
+    from oracle import orc
+    n0 = 4
+    N = 1 << n
+    nw = 40 if n <= 12 else 12
+    rng = np.random.default_rng(7000 + n)
+    prng = random.Random(7900 + n)
+    # information on the N / 8 positions of largest index weight outside those nodes: the channel words at
+    # pd <= 0.2 decode correctly, so every leaf is live and the words' decodes all differ
+    frozen = np.ones(N, np.uint8)
+    free = [i for i in range(N // 4, N) if not N // 2 <= i < N // 2 + N // 8]
+    frozen[sorted(free, key=lambda i: (bin(i).count("1"), i))[-(N // 8):]] = 0
+    fval = (rng.random(N) < 0.5).astype(np.uint8)
+    words = []
+    for i in range(nw - 4):
+        x = orc.encode_bin(rng.integers(0, 2, N // 8).astype(np.uint8), frozen, fval=fval)
+        words.append(tro.deletion_channel(tro.add_guard_bands([int(b) for b in x], n, n0, 0.1, 0),
+                                          (0.02, 0.1, 0.1, 0.2, 0.3, 0.45)[i % 6], prng))
+    words += [[], [1], [int(b) for b in rng.integers(0, 2, N // 3)], [int(b) for b in rng.integers(0, 2, N + N // 2)]]
+    W = max(len(w) for w in words)
+    rx = np.zeros((nw, W), np.uint8)
+    for i, w in enumerate(words):
+        rx[i, :len(w)] = w
+    ln = np.array([len(w) for w in words], np.int32)
+    pd = 0.1
+    i_ref, x_ref = orc.decode_deletion(rx, ln, n, n0, pd, frozen, fval)
+    # the words do decode differently: four channel words in six are at pd <= 0.2
+    assert len(set(i.tobytes() for i in i_ref)) >= 2 * (nw - 4) // 3
+    return frozen, fval, pd, rx, ln, i_ref, x_ref
+
+
+@pytest.mark.parametrize("n", [10, 12, 13, 14])
+def test_w4_persistent_loop(sc, n):
+    """k_sc_del_w4's codeword loop at each of its geometries (64 trellises; 256, tasks from a counter;
+    512, fixed-stride tasks, 12 waves; 1024, 10 waves): 5 x CUs + 3 codewords, so every workgroup of the
+    one-a-CU grid decodes several and the last round is ragged, drawn in a shuffled order from 40 (12 at
+    n = 13, 14) distinct words of very different lengths.  Every copy must decode as the C oracle decodes
+    its original, with the codewords taken from the per-launch counter and on the static stride: what one
+    codeword leaves in LDS (decision histories, information bits, task counters) or in the workgroup's
+    trellis cache must not reach the next."""
+    frozen, fval, pd, rx, ln, i_ref, x_ref = _w4_loop_words(n)
+    nw = rx.shape[0]
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    B = 5 * cus + 3
+    rng = np.random.default_rng(7100 + n)
+    order = np.concatenate([rng.permutation(nw) for _ in range(B // nw + 1)])[:B]
+    idx = torch.from_numpy(order).cuda()
+    rxb = torch.from_numpy(rx).cuda().index_select(0, idx)
+    lnb = torch.from_numpy(ln).cuda().index_select(0, idx)
+    want_i = torch.from_numpy(i_ref).cuda().index_select(0, idx)
+    want_x = torch.from_numpy(x_ref).cuda().index_select(0, idx)
+    d = sc.DeletionDecoder(sc.CodeSpec(1 << n, frozen, fval, device="cuda"), 4, pd)
+    old_wave = sc.set_deletion_wave(2)
+    old_dyn = sc.set_dynamic_tiles(1)
+    try:
+        if n != 10:
+            sc.set_deletion_wave(old_wave)  # n = 10: the wave kernel forced; beyond, the dispatch as shipped
+        for dyn in (1, 0):
+            sc.set_dynamic_tiles(dyn)
+            info, xhat = d.decode(rxb, lnb)
+            torch.cuda.synchronize()
+            bad = torch.nonzero((info != want_i).any(1) | (xhat != want_x).any(1)).flatten().tolist()
+            assert not bad, (n, dyn, len(bad), [(b, int(order[b])) for b in bad[:8]])
+    finally:
+        sc.set_dynamic_tiles(old_dyn)
+        sc.set_deletion_wave(old_wave)
+
+
+def test_dense_persistent_rounds_and_gated_fallback(sc):
+    """(n = 8, n0 = 2): 7 x CUs x 32 + 11 codewords, groups of 32 at 8 lanes a codeword, one group more a
+    CU than the resident grid's six workgroups, so both the table-driven kernel and its gated fallback
+    go round their loop again with a ragged last group.  300 distinct words in a shuffled order; with
+    the built table and with a foreign one (rejected on the device: the fallback decodes the whole batch
+    on its static stride), with the groups from the per-launch counter and on the static stride: each
+    equals the table-less decode, and the Python oracle on a sample of the distinct words."""
+    n, n0, pd = 8, 2, 0.1
+    N = 1 << n
+    rng = np.random.default_rng(8005)
+    prng = random.Random(8005)
+    frozen = (rng.random(N) < 0.5).astype(np.uint8)
+    fval = (rng.random(N) < 0.5).astype(np.uint8)
+    words = [tro.deletion_channel(tro.add_guard_bands([int(b) for b in rng.integers(0, 2, N)], n, n0, 0.1, 0),
+                                  (0.05, 0.1, 0.3)[t % 3], prng) for t in range(296)]
+    words += [[], [1], [0] * 9, [int(b) for b in rng.integers(0, 2, 2 * N)]]
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    B = 7 * cus * 32 + 11
+    order = np.concatenate([rng.permutation(300) for _ in range(B // 300 + 1)])[:B]
+    idx = torch.from_numpy(order).cuda()
+    rx0, ln0 = sc.pad_words(words)
+    rxb, lnb = rx0.index_select(0, idx), ln0.index_select(0, idx)
+    code = sc.CodeSpec(N, frozen, fval, device="cuda")
+    ref_i, ref_x = sc.DeletionDecoder(code, n0, pd, use_table=False).decode(rx0, ln0)
+    for i in list(range(0, 300, 23)) + [296, 297, 298, 299]:
+        x_ref, i_ref = tro.decode_deletion(words[i], n, n0, pd, frozen, fval)
+        assert ref_i[i].tolist() == i_ref and ref_x[i].tolist() == x_ref, i
+    want_i, want_x = ref_i.index_select(0, idx), ref_x.index_select(0, idx)
+    foreign = sc.DeletionDecoder(code, n0, 0.3).table(rxb.device)
+    old_dyn = sc.set_dynamic_tiles(1)
+    try:
+        for dyn in (1, 0):
+            sc.set_dynamic_tiles(dyn)
+            for tab in ("built", "foreign"):
+                d = sc.DeletionDecoder(code, n0, pd)
+                if tab == "foreign":
+                    d._tables[str(rxb.device)] = foreign
+                assert d.dense_layout(rxb.shape[1], rxb.device)
+                info, xhat = d.decode(rxb, lnb)
+                torch.cuda.synchronize()
+                assert torch.equal(info, want_i), (dyn, tab)
+                assert torch.equal(xhat, want_x), (dyn, tab)
+    finally:
+        sc.set_dynamic_tiles(old_dyn)
 
 
 def test_ragged_batches_match_single(sc):

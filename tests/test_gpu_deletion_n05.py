@@ -1,7 +1,8 @@
 """Deletion-channel SC decode of 32-input trellises (n0 = 5, main_deletion's n0 = n // 3 at n = 15) on
 the GPU: the wave-per-task kernel of sc_del_w5.hip / trellis_wave5.h at 64 .. 1024 trellises a codeword
 (n = 11 .. 15), bit-exact against the C oracle (oracle/trellis_oracle.c, pinned to the Python oracle at
-n0 = 5 by tests/test_emulated_deletion_n05.py), through the decoder class, the persistent loop, the
+n0 = 5 by tests/test_emulated_deletion_n05.py) and against the reference's own decodes
+(tests/golden/deletion_wave.npz), through the decoder class, the persistent loop, the
 facade, the launcher's length limit and the Monte-Carlo pipeline."""
 import ctypes
 import random
@@ -113,6 +114,19 @@ def test_wide_shapes_vs_c_oracle(sc, n, nch):
     i_ref, x_ref = orc.decode_deletion(rx, ln, n, N0, pd, frozen, fval)
     assert np.array_equal(info, i_ref)
     assert np.array_equal(xhat, x_ref)
+
+
+@pytest.mark.parametrize("n,pd", [(11, 0.1), (13, 0.2), (15, 0.1), (11, 0.05), (13, 0.1), (15, 0.05)])
+def test_wave_fixture(sc, n, pd):
+    """64, 256 and 1024 trellises of 32 inputs against the reference's own decodes
+    (tests/golden/deletion_wave.npz: channel words, one at pd 0.4, the empty word and an overlong one;
+    the first quarter frozen, so rate-0 depth-4 nodes; at rate 1/2, and at the rate 1/16 at which the
+    reference decodes correctly and every leaf is live): info and x_hat bit-exact."""
+    from tests.test_trellis_oracle import wave_case
+    c = wave_case(n, N0, pd)
+    info, xhat = _dec(sc, n, c["pd"], c["frozen"], c["fval"], c["rx"].copy(), c["rx_len"].copy())
+    assert np.array_equal(info, c["info"])
+    assert np.array_equal(xhat, c["xhat"])
 
 
 def test_persistent_loop(sc):

@@ -3,7 +3,8 @@ oracle/make_golden.py fx_edge_long): discrete, subnormal, random, one-sided zero
 quantised BI-AWGN at 2 dB (the rate-1 shortcut's common case), the same scaled to subnormal root
 products, a high-SNR channel whose ratios underflow, and 2 dB rows with 1 % defect letters — at
 N = 1024 and 4096, C2 / C3 Bhattacharyya and random frozen sets — through every built binary
-variant, including the shipped defaults 26 (N = 1024) and 31 (N = 4096) whose minus-transform
+variant, including the shipped defaults 26 (N = 1024), 30 (N = 4096) and 33 (N = 8192, 16384; 31 and
+24 are the fallbacks behind them) whose minus-transform
 division (`div_den12`) and rate-1 shortcut are exact by argument exactly at these inputs
 (sc_common.h, sc_bin_body.h; reference BinaryPolarEncoderDecoder.py:223-325,
 VectorDistributions/BinaryMemorylessVectorDistribution.py:15-87).  Bit-exact."""
@@ -55,7 +56,7 @@ def test_edge_long_bench_path(sc):
         assert np.array_equal(sc.unpack(tx, N).cpu().numpy(), c["xhat"]), (N, c["family_name"])
 
 
-@pytest.mark.parametrize("variant", [17, 26, 31])
+@pytest.mark.parametrize("variant", [17, 26, 30, 31])
 @pytest.mark.parametrize("idx", range(24))
 def test_edge_short_shipped_variants(sc, idx, variant):
     """The 24 short edge cases (N = 2..256) with the defaults selected: short codes take the
@@ -72,17 +73,17 @@ def test_edge_short_shipped_variants(sc, idx, variant):
         sc.set_variant()
 
 
-@pytest.mark.parametrize("variant", [24, 26, 31])
-def test_rate1_subnormal_ratios_n4096(sc, variant):
-    """N = 4096 rate-1 blocks at very high reliability, so that the products of ratios inside the
-    register subtrees reach the subnormal range and zero (the numerators `div_den12`'s exactness
-    argument singles out), mixed in the same waves with ties, (0, 0) rows and subnormal letters;
-    bit-exact against the oracle."""
+def _rate1_subnormal(sc, variant, N, B, runs=None):
+    """Rate-1 blocks at very high reliability, so that the products of ratios inside the register
+    subtrees reach the subnormal range and zero (the numerators `div_den12`'s exactness argument
+    singles out), mixed in the same waves with ties, (0, 0) rows and subnormal letters; bit-exact
+    against the oracle.  runs: the variant the launcher must pick at this length."""
     from oracle import orc
     sc.set_variant(variant)
     try:
-        rng = np.random.default_rng(4096 + variant)
-        N, B = 4096, 96
+        if runs is not None:
+            assert sc.variant_for(N.bit_length() - 1) == runs
+        rng = np.random.default_rng(N + variant)
         frozen = (rng.random(N) < 0.5).astype(np.uint8)
         w = N // 4
         while w >= 16:
@@ -108,3 +109,16 @@ def test_rate1_subnormal_ratios_n4096(sc, variant):
         assert np.array_equal(xhat.cpu().numpy(), rx)
     finally:
         sc.set_variant()
+
+
+@pytest.mark.parametrize("variant", [24, 26, 30, 31, 33])
+def test_rate1_subnormal_ratios_n4096(sc, variant):
+    """N = 4096 under the shipped default (30), its fallbacks (31, 24), the selected variant 26 (the
+    launcher's pick for it at this length) and 33."""
+    _rate1_subnormal(sc, variant, 4096, 96)
+
+
+def test_rate1_subnormal_ratios_n8192(sc):
+    """N = 8192 under the shipped default there, variant 33 (the split level at 8 lanes a codeword, bits
+    in the slot scratch)."""
+    _rate1_subnormal(sc, sc.default_variant(), 8192, 32, runs=33)

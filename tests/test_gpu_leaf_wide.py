@@ -2,7 +2,8 @@
 main_deletion's default n0 = n // 3; k_sc_del<4, 9|10, true, 0>, one codeword a workgroup of T
 threads): the supported range, every leaf's marginal bit-exact against the Python oracle on
 genie-mode inputs, decisions identical to the decode kernels, and leaves independent of the
-batch a word is decoded in."""
+batch a word is decoded in; and the export at 64, 256 and 512 trellises against the reference's own
+decodes (tests/golden/deletion_wave.npz)."""
 import random
 
 import numpy as np
@@ -159,6 +160,25 @@ def test_decisions_match_decode_kernels(sc, n, nwords):
         sc.set_deletion_wave(old)
     mi = m[:, frozen == 0]
     assert np.array_equal((mi[..., 0] < mi[..., 1]).astype(np.uint8), info_l)
+
+
+@pytest.mark.parametrize("n,pd", [(10, 0.1), (12, 0.25), (13, 0.1), (10, 0.05), (12, 0.1), (13, 0.05)])
+def test_leaves_match_reference_fixture(sc, n, pd):
+    """Leaf export at 64, 256 and 512 trellises of 16 inputs against the reference's own decodes
+    (tests/golden/deletion_wave.npz, both frozen sets of each shape): info and x_hat of every word
+    bit-exact, and the marginals at the information leaves bit-exact for the words whose marginals the
+    fixture stores (all eight at n = 10, the first two or the first at n = 12, 13)."""
+    from tests.test_trellis_oracle import wave_case
+    c = wave_case(n, N0, pd)
+    assert c["nleaf"] >= 1
+    code = sc.CodeSpec(1 << n, c["frozen"], c["fval"], device="cuda")
+    info, xhat, m = sc.DeletionDecoder(code, N0, c["pd"]).decode_leaves(torch.from_numpy(c["rx"].copy()).cuda(),
+                                                                         torch.from_numpy(c["rx_len"].copy()).cuda())
+    torch.cuda.synchronize()
+    assert np.array_equal(info.cpu().numpy(), c["info"])
+    assert np.array_equal(xhat.cpu().numpy(), c["xhat"])
+    infopos = c["frozen"] == 0
+    assert np.array_equal(m[:c["nleaf"]].cpu().numpy()[:, infopos], c["leaf_m"][:, infopos])
 
 
 def test_ragged_batch(sc):

@@ -143,3 +143,66 @@ def test_qary_rate1_blocks(lanes):
         ri, rx = orc.decode_qary(q, xy, frozen)
         assert np.array_equal(info.cpu().numpy(), ri), (N, lanes)
         assert np.array_equal(xhat.cpu().numpy(), rx), (N, lanes)
+
+
+def _decode_qary_c(sc, code, native, ws_bytes):
+    """pcub_sc_decode_qary on [N, B, q] rows with a workspace of exactly ws_bytes bytes."""
+    from polarcub_amd import _lib
+    B = native.shape[1]
+    info = torch.zeros((max(1, code.K), B), dtype=torch.uint8, device="cuda")
+    xh = torch.zeros((code.N, B), dtype=torch.uint8, device="cuda")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+    rc = _lib.lib().pcub_sc_decode_qary(sc._p(native), B, code.n, code.q, sc._p(code.frozen_dev), code.K, sc._p(info),
+                                        sc._p(xh), sc._p(ws), ws.numel(), sc._stream())
+    assert rc == 0
+    torch.cuda.synchronize()
+    return info[:code.K].t().contiguous(), xh.t().contiguous()
+
+
+@pytest.mark.parametrize("q,N", [(4, 256), (3, 64)])
+def test_qary_tile_loop_both_schedulers(q, N):
+    """1,007 codewords with the workspace for one codeword (the launcher clamps the grid to one workgroup,
+    which goes over every wave tile, the last one ragged) and with the workspace for all of them, the
+    tiles from the per-launch counter and on the static stride: all four equal the oracle.  At q = 4,
+    N = 256 (the C4 kernel) also three rounds of the full grid plus five codewords, 256 distinct rows
+    repeated in a shuffled order."""
+    from oracle import orc
+    from polarcub_amd import _lib, sc
+    n = N.bit_length() - 1
+    B = 1000 + 7
+    rng = np.random.default_rng(900 + q)
+    frozen = (rng.random(N) < 0.4).astype(np.uint8)
+    frozen[N // 2: N // 2 + N // 8] = 1
+    xy = rng.random((B, N, q))
+    xy[rng.random((B, N)) < 0.05] = 0.0
+    ri, rx = orc.decode_qary(q, xy, frozen)
+    code = sc.QaryCode(q, N, frozen, device="cuda")
+    native = torch.from_numpy(np.ascontiguousarray(xy.transpose(1, 0, 2))).cuda()
+    L = _lib.lib()
+    one, full = int(L.pcub_sc_decode_qary_workspace(1, n, q)), int(L.pcub_sc_decode_qary_workspace(B, n, q))
+    assert 0 < one < full
+    old = sc.set_dynamic_tiles(1)
+    try:
+        for dyn in (1, 0):
+            sc.set_dynamic_tiles(dyn)
+            for ws in (one, full):
+                info, xhat = _decode_qary_c(sc, code, native, ws)
+                assert np.array_equal(info.cpu().numpy(), ri), (dyn, ws)
+                assert np.array_equal(xhat.cpu().numpy(), rx), (dyn, ws)
+            if (q, N) == (4, 256):
+                dec = sc.QaryDecoder(code)
+                cwb = 4 * dec.tile()  # codewords a workgroup of four waves
+                # the grid the launcher saturates at, from its workspace: one workgroup's slots are what a
+                # second tile adds
+                per_wg = int(L.pcub_sc_decode_qary_workspace(cwb + 1, n, q)) - one
+                grid = (int(L.pcub_sc_decode_qary_workspace(1 << 22, n, q)) - one) // per_wg + 1
+                assert grid >= torch.cuda.get_device_properties(0).multi_processor_count
+                Bg = 3 * grid * cwb + 5
+                order = np.concatenate([rng.permutation(256) for _ in range(Bg // 256 + 1)])[:Bg]
+                idx = torch.from_numpy(order).cuda()
+                gi, gx = dec.decode_native(native[:, :256].index_select(1, idx))
+                torch.cuda.synchronize()
+                assert torch.equal(gi.t(), torch.from_numpy(ri[:256]).cuda().index_select(0, idx)), dyn
+                assert torch.equal(gx.t(), torch.from_numpy(rx[:256]).cuda().index_select(0, idx)), dyn
+    finally:
+        sc.set_dynamic_tiles(old)

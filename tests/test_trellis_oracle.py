@@ -22,6 +22,51 @@ def deletion_edge_cases():
     return out
 
 
+_WAVE = None
+
+
+def deletion_wave_cases():
+    """tests/golden/deletion_wave.npz (oracle/make_golden.py fx_deletion_wave): the reference's decodes
+    at the shapes of the wave-per-task kernels, one dict a case with n, n0, pd, nch (channel words),
+    nleaf (the first words, whose marginals at the information leaves are stored: leaf_m) and low (1: the frozen set keeps N / 16
+    reliable positions, so the reference decodes the channel words correctly and every leaf is live;
+    0: rate about 1/2 at random, where a channel word's decode goes wrong early and most later leaves
+    are ties); loaded once and left unchanged."""
+    global _WAVE
+    if _WAVE is None:
+        g = load_golden("deletion_wave")
+        out = []
+        for i in range(g["meta"]["cases"]):
+            c = {k.split("_", 1)[1]: v for k, v in g.items() if k.startswith("c%d_" % i)}
+            c["n"], c["n0"], ones, c["nch"], c["low"] = (int(v) for v in c["shape"])
+            assert ones == 0
+            c["pd"] = float(c["pd"][0])
+            c["nleaf"] = c["leaf_mi"].shape[0]
+            # the stored marginals (information leaves only) at their positions, zeros elsewhere
+            c["leaf_m"] = np.zeros((c["nleaf"], 1 << c["n"], 2))
+            c["leaf_m"][:, c["frozen"] == 0] = c["leaf_mi"]
+            for v in c.values():
+                if isinstance(v, np.ndarray):
+                    v.setflags(write=False)
+            out.append(c)
+        _WAVE = out
+    return _WAVE
+
+
+def wave_case(n, n0, pd=None):
+    """The fixture's case of shape (n, n0) (and deletion rate pd where a shape has two)."""
+    hits = [c for c in deletion_wave_cases() if (c["n"], c["n0"]) == (n, n0) and pd in (None, c["pd"])]
+    assert len(hits) == 1, (n, n0, pd)
+    return hits[0]
+
+
+# (n, n0, pd) of every case of deletion_wave.npz: rate about 1/2, then (WAVE_LOW) rate 1/16
+WAVE_HALF = [(6, 5, 0.1), (6, 5, 0.25), (7, 5, 0.1), (7, 5, 0.25), (10, 4, 0.1), (11, 5, 0.1), (12, 4, 0.25),
+             (13, 4, 0.1), (14, 4, 0.1), (13, 5, 0.2), (15, 5, 0.1)]
+WAVE_LOW = [(10, 4, 0.05), (11, 5, 0.05), (12, 4, 0.1), (13, 4, 0.05), (14, 4, 0.05), (13, 5, 0.1), (15, 5, 0.05)]
+WAVE_SHAPES = WAVE_HALF + WAVE_LOW
+
+
 def _check(words, n, n0, pd, ones, frozen, fval, info, xhat, leaf_m):
     for t, w in enumerate(words):
         lm = []
@@ -124,6 +169,49 @@ def test_c_oracle_matches_reference():
         n, n0, ones = (int(v) for v in c["shape"])
         info, xhat = orc.decode_deletion(c["rx"], c["rx_len"], n, n0, float(c["pd"][0]), c["frozen"], c["fval"], ones)
         assert np.array_equal(info, c["info"]) and np.array_equal(xhat, c["xhat"])
+
+
+def test_wave_fixture_is_not_vacuous():
+    """deletion_wave.npz holds the cases the tests below name, every one with information bits,
+    decisions that differ between words, and (five words or more) segments of 0 symbols, of 1 .. 2^n0
+    and of more than 2^n0."""
+    cases = deletion_wave_cases()
+    assert [(c["n"], c["n0"], c["pd"]) for c in cases] == WAVE_SHAPES
+    for c in cases:
+        n, n0, T = c["n"], c["n0"], c["rx"].shape[0]
+        assert c["info"].shape[1] > 0 and c["info"].shape[1] == int((c["frozen"] == 0).sum())
+        assert c["frozen"][: (1 << n) // 4].all() and 0 < c["fval"][c["frozen"] == 1].mean() < 1
+        assert any(not np.array_equal(c["info"][t], c["info"][u]) for t in range(c["nch"]) for u in range(T))
+        lens = set(len(s) for w in _words(c) for s in tro.remove_guard_bands(w, n, n0))
+        if T >= 5:
+            assert 0 in lens and any(1 <= l <= 1 << n0 for l in lens) and max(lens) > 1 << n0
+        assert c["low"] == ((n, n0, c["pd"]) in WAVE_LOW)
+        if c["low"]:  # a live decode: the reference decodes a channel word at the case's pd correctly
+            assert any(np.array_equal(c["info"][t], c["tx_info"][t]) for t in range(max(1, c["nch"] - 1)))
+            assert 0.3 < c["info"][0].mean() < 0.7
+
+
+@pytest.mark.parametrize("n,n0,pd", WAVE_SHAPES)
+def test_c_oracle_matches_wave_fixture(n, n0, pd):
+    """oracle/trellis_oracle.c against the reference's own decodes at the shapes of the wave-per-task
+    kernels (n0 = 4 at n = 10 .. 14, n0 = 5 at n = 6, 7, 11, 13, 15): info and x_hat bit-exact, every
+    word of every case."""
+    from oracle import orc
+    c = wave_case(n, n0, pd)
+    info, xhat = orc.decode_deletion(c["rx"], c["rx_len"], n, n0, pd, c["frozen"], c["fval"], 0)
+    assert np.array_equal(info, c["info"])
+    assert np.array_equal(xhat, c["xhat"])
+
+
+@pytest.mark.parametrize("n,pd,nwords", [(10, 0.1, 8), (10, 0.05, 8), (12, 0.25, 2), (12, 0.1, 1)])
+def test_python_oracle_matches_wave_fixture_n04(n, pd, nwords):
+    """oracle/trellis_oracle.py against the reference at (10, 4) (every word) and (12, 4) (the words
+    whose leaf marginals are stored), both frozen sets: info, x_hat and the marginals at information
+    leaves bit-exact.  The larger cases are left to the C oracle above: the Python restatement takes
+    seconds a word there.  The n0 = 5 cases are in tests/test_emulated_deletion_n05.py."""
+    c = wave_case(n, 4, pd)
+    assert c["nleaf"] >= nwords
+    _check(_words(c)[:nwords], n, 4, c["pd"], 0, c["frozen"], c["fval"], c["info"], c["xhat"], c["leaf_m"])
 
 
 # (12, 4, 0), (13, 4, 0): main_deletion's own n0 = n // 3 at n = 12, 13 (256 and 512 trellises of
