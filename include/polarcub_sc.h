@@ -195,8 +195,9 @@ int pcub_sc_decode_qary_log(const double* xy, int64_t B, int32_t q, int32_t log2
 
 /* q-ary SCL / Fast-SSC list decoding (QaryPolarEncoderDecoder.listDecode,
  * QaryPolarEncoderDecoder.py:118-227, 403-820; rate-0, repetition, rate-1 and single-parity-check
- * nodes as the reference), linear domain, one lane per codeword.
- *   xy           [N][B][q] f64; q in 2..8, log2N in 0..12, L (maxListSize) in 1..64
+ * nodes as the reference), linear domain.  L <= 64: one lane per codeword; above: one workgroup
+ * per codeword with the lanes over paths and candidates (same results, same tie rules).
+ *   xy           [N][B][q] f64; q in 2..8, log2N in 0..12, L (maxListSize) in 1..PCUB_SCL_MAX_L
  *   frozen       [N] u8 (1 = frozen); frozen_vals [nF][B] u8 frozen values in frozen-index order
  *   actual       [K][B] u8 actual information (listDecode's actualInformation) or NULL
  *   out_info     [L][K][B] u8 final list (rows >= out_size: 0xff); out_prob [L][B] f64 metrics
@@ -204,7 +205,10 @@ int pcub_sc_decode_qary_log(const double* xy, int64_t B, int32_t q, int32_t log2
  * Ties among candidate metrics / reliabilities go to the lower index and the list is kept in
  * ascending candidate order (the reference's order comes from numpy's argpartition, which is
  * CPU-dependent); without ties the final path set and metrics are the reference's.
- * Workspace: pcub_scl_qary_workspace(B, q, log2N, L, K) bytes. */
+ * Workspace: pcub_scl_qary_workspace(B, q, log2N, L, K) bytes (the resident slots of a launch; a
+ * smaller workspace is accepted down to one workgroup's slots, fewer slots then stride over the
+ * batch; PCUB_EINVAL when not even those fit). */
+#define PCUB_SCL_MAX_L 4096
 size_t pcub_scl_qary_workspace(int64_t B, int32_t q, int32_t log2N, int32_t L, int32_t K);
 int pcub_scl_qary(const double* xy, int64_t B, int32_t q, int32_t log2N, int32_t L, const uint8_t* frozen,
                   const uint8_t* frozen_vals, int32_t nF, const uint8_t* actual, int32_t K, uint8_t* out_info,
@@ -222,6 +226,12 @@ int pcub_scl_qary_log(const double* xy, int64_t B, int32_t q, int32_t log2N, int
                       const uint8_t* frozen_vals, int32_t nF, const uint8_t* actual, int32_t K, uint8_t* out_info,
                       double* out_prob, int32_t* out_size, double* out_actual, void* workspace,
                       size_t workspace_bytes, void* stream);
+
+/* Diagnostic, not part of the stable ABI: which kernel the list decoder runs.  0: automatic
+ * (L <= 64 the lane kernel, above the workgroup kernel); 1: the lane kernel (calls with L > 64
+ * then fail with PCUB_EINVAL); 2: the workgroup kernel at any L.  pcub_scl_qary_workspace follows
+ * the mode.  Returns the previous mode, or -1 for any other value (nothing changes). */
+int pcub_scl_set_layout(int32_t mode);
 
 /* Non-uniform a-priori distribution (two trees).  Replaces recursiveEncodeDecode with an
  * xVectorDistribution that is not uniform (BinaryPolarEncoderDecoder.py:223-325, called by

@@ -112,6 +112,8 @@ def lib():
                                 _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, ctypes.c_size_t, _c_void_p]
     L.pcub_scl_qary_log.restype = ctypes.c_int
     L.pcub_scl_qary_log.argtypes = L.pcub_scl_qary.argtypes
+    L.pcub_scl_set_layout.restype = ctypes.c_int
+    L.pcub_scl_set_layout.argtypes = [_i32]
     L.pcub_sc_decode_qary_log_workspace.restype = ctypes.c_size_t
     L.pcub_sc_decode_qary_log_workspace.argtypes = [_i64, _i32, _i32]
     L.pcub_sc_decode_qary_log.restype = ctypes.c_int
@@ -199,7 +201,7 @@ EXPORTS = ["pcub_abi_version", "pcub_sc_decode_bin_workspace", "pcub_sc_decode_b
            "pcub_sc_leaf_deletion_supported", "pcub_sc_decode_deletion", "pcub_sc_leaf_bin_workspace", "pcub_sc_leaf_bin", "pcub_sc_leaf_deletion",
            "pcub_sc_prior_bin_workspace", "pcub_sc_prior_bin",
            "pcub_sc_decode_qary_log_workspace", "pcub_sc_decode_qary_log",
-           "pcub_scl_qary_workspace", "pcub_scl_qary", "pcub_scl_qary_log", "pcub_leaf_marginals", "pcub_mc_info", "pcub_mc_channel", "pcub_mc_count_errors", "pcub_mc_channel_norm", "pcub_sc_decode_bin_compact_direct", "pcub_sc_decode_bin_compact_workspace",
+           "pcub_scl_qary_workspace", "pcub_scl_qary", "pcub_scl_qary_log", "pcub_scl_set_layout", "pcub_leaf_marginals", "pcub_mc_info", "pcub_mc_channel", "pcub_mc_count_errors", "pcub_mc_channel_norm", "pcub_sc_decode_bin_compact_direct", "pcub_sc_decode_bin_compact_workspace",
            "pcub_sc_decode_bin_compact", "pcub_mc_info_qary", "pcub_mc_channel_qsc", "pcub_mc_deletion",
            "pcub_mc_run_bin_workspace", "pcub_mc_run_bin", "pcub_sc_deletion_table_bytes",
            "pcub_sc_deletion_build_table", "pcub_sc_decode_deletion_tab", "pcub_sc_leaf_deletion_tab",

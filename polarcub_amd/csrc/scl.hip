@@ -10,16 +10,33 @@
 // 1.65 k cw/s at q = 4, N = 4096, L = 32 and removed)
 // List decoding is a host-side tool in the reference
 // (the IR simulation); the kernel batches it, it is not the SC throughput path.
+// Lists above 64 paths run k_scl_wg (scl_wg.hip): a workgroup a codeword, lanes over paths and
+// candidates; pcub_scl_set_layout forces either kernel for A/B runs.
 #include <hip/hip_runtime.h>
+
+#include <atomic>
 
 #include "polarcub_sc.h"
 #include "scl_body.h"
+#include "scl_wg.h"
 
 using namespace pcub;
 
 namespace {
 
 constexpr int kSclBlock = 64;
+constexpr int kSclLaneMaxL = 64;  // k_scl's private origin[] and serial prune
+
+// 0: automatic (L <= 64: k_scl, above: k_scl_wg); 1: k_scl; 2: k_scl_wg (pcub_scl_set_layout)
+std::atomic<int> g_scl_layout{0};
+
+// whether a call at list size L runs the workgroup kernel; false with *ok = false when the
+// forced lane kernel cannot take L
+bool scl_use_wg(int32_t L, bool* ok) {
+    const int mode = g_scl_layout.load();
+    *ok = !(mode == 1 && L > kSclLaneMaxL);
+    return mode == 2 || (mode == 0 && L > kSclLaneMaxL);
+}
 
 __global__ __launch_bounds__(kSclBlock) void k_scl(SclArgs A) {
     const long long slot = (long long)blockIdx.x * kSclBlock + threadIdx.x;
@@ -32,7 +49,7 @@ __global__ __launch_bounds__(kSclBlock) void k_scl(SclArgs A) {
 }
 
 bool scl_args_ok(int64_t B, int32_t q, int32_t log2N, int32_t L, int32_t K) {
-    return B >= 0 && q >= 2 && q <= 8 && log2N >= 0 && log2N <= 12 && L >= 1 && L <= 64 && K >= 0 &&
+    return B >= 0 && q >= 2 && q <= 8 && log2N >= 0 && log2N <= 12 && L >= 1 && L <= PCUB_SCL_MAX_L && K >= 0 &&
            K <= (1 << log2N);
 }
 
@@ -57,8 +74,17 @@ size_t scl_slot_bytes(int32_t q, int32_t log2N, int32_t L, int32_t K) {
 
 }  // namespace
 
+extern "C" int pcub_scl_set_layout(int32_t mode) {
+    if (mode < 0 || mode > 2) return -1;
+    return g_scl_layout.exchange(mode);
+}
+
 extern "C" size_t pcub_scl_qary_workspace(int64_t B, int32_t q, int32_t log2N, int32_t L, int32_t K) {
     if (B <= 0 || !scl_args_ok(B, q, log2N, L, K)) return 0;
+    bool ok;
+    const bool wg = scl_use_wg(L, &ok);
+    if (!ok) return 0;
+    if (wg) return (size_t)scl_wg_grid(B) * scl_wg_slot_bytes(q, log2N, L, K) + 16;
     return (size_t)scl_slots(B) * scl_slot_bytes(q, log2N, L, K) + 16;
 }
 
@@ -72,6 +98,33 @@ int launch_scl(bool lg, const double* xy, int64_t B, int32_t q, int32_t log2N, i
     if (B == 0) return 0;
     if (!xy || (nF > 0 && !frozen_vals) || !out_info || !out_prob || !out_size || !workspace) return PCUB_EINVAL;
     if (actual && !out_actual) return PCUB_EINVAL;
+    bool ok;
+    const bool wg = scl_use_wg(L, &ok);
+    if (!ok) return PCUB_EINVAL;
+    if (wg) {
+        long long g = scl_wg_grid(B);
+        if (g <= 0) return (int)hipErrorNoDevice;
+        const size_t per_slot = scl_wg_slot_bytes(q, log2N, L, K);
+        if ((size_t)g * per_slot > workspace_bytes) g = (long long)(workspace_bytes / per_slot);
+        if (g <= 0) return PCUB_EINVAL;
+        SclArgs A;
+        A.xy = xy;
+        A.B = B;
+        A.n = log2N;
+        A.q = q;
+        A.L = L;
+        A.K = K;
+        A.frozen = frozen;
+        A.fvals = frozen_vals;
+        A.nF = nF;
+        A.actual = actual;
+        A.out_info = out_info;
+        A.out_prob = out_prob;
+        A.out_size = (int*)out_size;
+        A.out_actual = out_actual;
+        A.log = lg ? 1 : 0;
+        return scl_wg_launch(A, g, workspace, stream);
+    }
     long long g = scl_grid(B);
     if (g <= 0) return (int)hipErrorNoDevice;
     const size_t per_block = (size_t)kSclBlock * scl_slot_bytes(q, log2N, L, K);

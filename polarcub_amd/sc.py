@@ -595,16 +595,30 @@ class QaryLogDecoder:
         return out + (leaf.transpose(0, 1).contiguous(),) if want_leaf else out
 
 
+SCL_MAX_L = 4096  # PCUB_SCL_MAX_L (include/polarcub_sc.h)
+
+
+def set_scl_layout(mode):
+    """Diagnostic (pcub_scl_set_layout): which kernel the list decoder runs.  0: automatic (L <= 64
+    one lane a codeword, above one workgroup a codeword); 1: the lane kernel (L <= 64 only); 2: the
+    workgroup kernel at any L.  Returns the previous mode."""
+    prev = int(_lib.lib().pcub_scl_set_layout(int(mode)))
+    if prev < 0:
+        raise ValueError("list decoder layout mode must be 0, 1 or 2, got %r" % (mode,))
+    return prev
+
+
 class QaryListDecoder:
     """Batched q-ary SCL / Fast-SSC list decoding (pcub_scl_qary): QaryPolarEncoderDecoder.listDecode
-    for B codewords of one code at list size L, with optional actual information words."""
+    for B codewords of one code at list size L (up to SCL_MAX_L), with optional actual information
+    words."""
 
     def __init__(self, q, N, frozen_mask, L, device=None, use_log=False):
         self.q, self.N, self.L = int(q), int(N), int(L)
         self.use_log = bool(use_log)  # log-probability rows and metrics (pcub_scl_qary_log)
         self.n = _log2(self.N)
-        if not 2 <= self.q <= 8 or not 1 <= self.L <= 64 or self.n > 12:
-            raise ValueError("list decoder needs 2 <= q <= 8, 1 <= L <= 64, N <= 4096")
+        if not 2 <= self.q <= 8 or not 1 <= self.L <= SCL_MAX_L or self.n > 12:
+            raise ValueError("list decoder needs 2 <= q <= 8, 1 <= L <= %d, N <= 4096" % SCL_MAX_L)
         mask = (np.asarray(frozen_mask, dtype=np.uint8).reshape(-1) != 0).astype(np.uint8)
         if mask.shape[0] != self.N:
             raise ValueError("frozen mask has %d entries, expected N=%d" % (mask.shape[0], self.N))
