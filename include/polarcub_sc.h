@@ -348,6 +348,47 @@ int pcub_mc_run_deletion(uint64_t seed, int64_t offset, int64_t count, int32_t n
                          int32_t K, const double* table, int64_t chunk, uint64_t* counters, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* Information reconciliation over QSC(p) as one device pipeline (irSimulation,
+ * QaryPolarEncoderDecoder.py:887-930, with listDecode's actualInformation verdict, :172-213), for
+ * global codewords under the same (seed, g) keying as above.
+ *   pcub_ir_prepare   one trial's inputs for codewords [offset, offset + B):
+ *       a            [N][B] u8: what pcub_mc_info_qary(seed, offset, B, K = N, q) writes
+ *       xy           [N][B][q] f64: what pcub_mc_channel_qsc(seed, offset, B, log2N, q, p, x = a)
+ *                    writes; with use_log != 0 each entry's logarithm (std::log of the row's two
+ *                    values, taken on the host)
+ *       actual       [K][B] u8, frozen_vals [nF][B] u8: u = polarTransformOfQudits(q, a) (:1136-1154)
+ *                    on the information / frozen positions of frozen ([N] u8, 1 = frozen, K zeros),
+ *                    in ascending index order: pcub_scl_qary's actual and frozen_vals (ir()'s
+ *                    frozen_values = u (q - 1)^2 mod q = u, :822-846)
+ *       work         [N][B] u8 scratch
+ *     q in 2..8, log2N in 0..12, p in [0, 1].
+ *   pcub_ir_classify  the verdict on pcub_scl_qary's outputs out_info [L][K][B], out_prob [L][B],
+ *     out_size [B], out_actual [B] against actual [K][B].  The match is the lowest i < out_size
+ *     whose K symbols equal the key (K = 0: i = 0).  With a match the outcome is 0 when
+ *     prob[i] == max(prob[:size]), else 1; without, 2 / 3 / 4 / 5 by actual_prob > max, == max,
+ *     >= min(prob[:size]), else (ProbResult, :18-24), the key is bad and its bad symbols are the
+ *     Hamming distance between the key and path 0.  counters (device u64[10], accumulating, the
+ *     caller zeroes them): [0] trials, [1] bad keys, [2] bad symbols, [3] sum of list sizes,
+ *     [4 + r] trials of outcome r.  results [B] u8 outcome codes, or NULL.
+ *   pcub_mc_run_ir    prepare -> pcub_scl_qary (use_log: pcub_scl_qary_log) with the actual path ->
+ *     classify for codewords [offset, offset + count), chunk at a time on the stream, no host
+ *     synchronisation; results u8[count] or NULL.  Workspace: pcub_mc_run_ir_workspace(chunk, q,
+ *     log2N, L, K) bytes hold the chunk's buffers and the list decoder's full slab; any workspace
+ *     that holds the chunk's buffers and pcub_scl_qary_workspace(1, ...) more is accepted (the
+ *     decoder then strides fewer slots over the chunk).  PCUB_EINVAL before any launch: NULL
+ *     counters or frozen, q outside 2..8, L outside 1..PCUB_SCL_MAX_L, log2N > 12, p outside
+ *     [0, 1], negative count or offset, chunk <= 0, a workspace that is too small. */
+int pcub_ir_prepare(uint64_t seed, int64_t offset, int64_t B, int32_t log2N, int32_t q, double p, int32_t use_log,
+                    const uint8_t* frozen, int32_t K, uint8_t* a, double* xy, uint8_t* actual, uint8_t* frozen_vals,
+                    uint8_t* work, void* stream);
+int pcub_ir_classify(const uint8_t* out_info, const double* out_prob, const int32_t* out_size,
+                     const double* out_actual, const uint8_t* actual, int64_t B, int32_t L, int32_t K,
+                     uint64_t* counters, uint8_t* results, void* stream);
+size_t pcub_mc_run_ir_workspace(int64_t chunk, int32_t q, int32_t log2N, int32_t L, int32_t K);
+int pcub_mc_run_ir(uint64_t seed, int64_t offset, int64_t count, int32_t log2N, int32_t q, double p, int32_t L,
+                   int32_t use_log, const uint8_t* frozen, int32_t K, int64_t chunk, uint64_t* counters,
+                   uint8_t* results, void* workspace, size_t workspace_bytes, void* stream);
+
 /* [B][nbits] u8 (0/1) -> ceil(nbits/32) x B words, and back. */
 int pcub_pack_bits(const uint8_t* bits, int64_t B, int32_t nbits, uint32_t* words, void* stream);
 int pcub_unpack_bits(const uint32_t* words, int64_t B, int32_t nbits, uint8_t* bits, void* stream);

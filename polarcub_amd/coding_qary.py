@@ -468,6 +468,40 @@ def irSimulation(q, length, simulateChannel, make_xyVectorDistribution, numberOf
     return frame_error_prob, symbol_error_prob, rate, probResultList
 
 
+def irSimulationDevice(q, length, p, numberOfTrials, frozenSet, maxListSize=1, seed=1, use_log=False, verbosity=0):
+    """irSimulation over the q-ary symmetric channel QSC(p) as one device pipeline (mc.run_ir:
+    the draws, the syndrome / key split, the list decode and listDecode's verdict all stay on the
+    GPU; only ten counters and one outcome code a trial come back).  Returns irSimulation's four
+    values (frame_error_prob, symbol_error_prob, rate, probResultList) and prints its three lines
+    when verbosity is set.
+
+    Two differences from irSimulation:
+      * the information word and the channel are drawn from Philox4x32-10 streams keyed by
+        (seed, trial index) instead of the reference's MT19937 streams, so the trials are different
+        trials of the same law (uniform a, b = QSC_p(a)), not the reference's trials;
+      * the frozen values reach the decoder in ascending index order of the frozen set (and the key
+        in ascending order of the information set), whatever order frozenSet is given in.
+    """
+    import torch
+
+    from . import mc, sc
+    mask = np.zeros(length, np.uint8)
+    mask[sorted(frozenSet)] = 1
+    code = sc.QaryCode(q, length, mask, device=torch.device("cuda"))
+    counters, codes = mc.run_ir(code, seed, 0, numberOfTrials, p, maxListSize, use_log=use_log, results=True)
+    badKeys, badSymbols = counters[1], counters[2]
+    probResultList = [ProbResult(int(c)) for c in codes]
+    rate = (math.log2(q) * code.K - math.log2(maxListSize)) / length
+    frame_error_prob = badKeys / numberOfTrials
+    symbol_error_prob = badSymbols / (numberOfTrials * length)
+    if verbosity:
+        print("Rate: ", rate)
+        print("Frame error probability = ", badKeys, "/", numberOfTrials, " = ", frame_error_prob)
+        print("Symbol error probability = ", badSymbols, "/ (", numberOfTrials, " * ", length, ") = ",
+              symbol_error_prob)
+    return frame_error_prob, symbol_error_prob, rate, probResultList
+
+
 def polarTransformOfQudits(q, xvec):
     """x -> u for the q-ary convention (QaryPolarEncoderDecoder.py:1136-1154)."""
     x = np.asarray(xvec, dtype=np.int64)

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "polarcub_sc.h"
+#include "mc_rng.h"
 #include "sc_common.h"
 
 using namespace pcub;
@@ -22,37 +23,6 @@ using namespace pcub;
 namespace {
 
 constexpr int kMcBlock = 256;
-
-// Philox4x32-10 (Salmon et al., SC'11): counter (c0..c3), key (k0, k1).
-struct P4 {
-    uint32_t v[4];
-};
-
-PCUB_HD P4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)M0 * c0, p1 = (uint64_t)M1 * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1;
-        c3 = (uint32_t)p0;
-        c0 = n0;
-        c2 = n2;
-        k0 += W0;
-        k1 += W1;
-    }
-    return P4{{c0, c1, c2, c3}};
-}
-
-// streams inside one codeword's counter space
-constexpr uint32_t kStreamInfo = 0, kStreamChannel = 1;
-
-// uniform double in (0, 1] from 53 random bits
-PCUB_HD double u01(uint32_t hi, uint32_t lo) {
-    const uint64_t m = (((uint64_t)hi << 32) | lo) >> 11;
-    return ((double)m + 1.0) * (1.0 / 9007199254740992.0);
-}
 
 struct McArgs {
     uint64_t seed;
@@ -302,9 +272,6 @@ __global__ __launch_bounds__(kMcBlock) void k_mc_count_sym(const uint8_t* dec, c
 
 unsigned grid_of(long long work) { return (unsigned)((work + kMcBlock - 1) / kMcBlock); }
 
-// uniform symbol in [0, m) from 32 random bits (multiply-shift)
-PCUB_HD uint32_t below(uint32_t r, uint32_t m) { return (uint32_t)(((uint64_t)r * m) >> 32); }
-
 // q-ary information symbols [K][B] u8: symbol k of codeword g is below(q) of Philox output
 // lane (k & 3) of counter (g, kStreamInfo, k >> 2)
 __global__ __launch_bounds__(kMcBlock) void k_mc_info_qary(McArgs A, int q, uint8_t* info) {
@@ -332,8 +299,7 @@ __global__ __launch_bounds__(kMcBlock) void k_mc_qsc(McArgs A, int q, const uint
         const P4 r = philox((uint32_t)g, (uint32_t)(g >> 32), kStreamChannel, (uint32_t)i, (uint32_t)A.seed,
                             (uint32_t)(A.seed >> 32));
         const int xs = x[i * A.B + b];
-        const bool err = u01(r.v[0], r.v[1]) <= A.param;
-        const int y = err ? (xs + 1 + (int)below(r.v[2], q - 1)) % q : xs;
+        const int y = qsc_output(r, q, A.param, xs);
         double* row = xy + row_at(A, i, b) * q;
         for (int t = 0; t < q; ++t) row[t] = t == y ? hit : miss;
     }

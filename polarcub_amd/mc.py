@@ -220,6 +220,83 @@ def run_deletion(code, seed, offset, count, n0, xi, pd, ones=0, table=None, chun
     return [int(v) for v in counters.tolist()]
 
 
+def ir_prepare(code, seed, offset, B, p, use_log=False):
+    """One IR trial's inputs for global codewords [offset, offset + B) (pcub_ir_prepare): the drawn
+    word a [N, B] u8, its QSC(p) rows xy [N, B, q] f64 (their logarithms with use_log), and
+    u = polarTransformOfQudits(q, a) on the information positions (actual [K, B] u8, the key) and on
+    the frozen positions (frozen_vals [nF, B] u8), both in ascending index order."""
+    from . import _lib
+    dev = code.device
+    nF = code.N - code.K
+    a = torch.empty((code.N, B), dtype=torch.uint8, device=dev)
+    work = torch.empty((code.N, B), dtype=torch.uint8, device=dev)
+    xy = torch.empty((code.N, B, code.q), dtype=torch.float64, device=dev)
+    actual = torch.zeros((max(1, code.K), B), dtype=torch.uint8, device=dev)
+    fv = torch.zeros((max(1, nF), B), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.lib().pcub_ir_prepare(int(seed), int(offset), B, code.n, code.q, float(p), 1 if use_log else 0,
+                                          sc._p(code.frozen_dev), code.K, sc._p(a), sc._p(xy), sc._p(actual),
+                                          sc._p(fv), sc._p(work), sc._stream()), "pcub_ir_prepare")
+    return a, xy, actual[:code.K], fv[:nF]
+
+
+def ir_classify(info, prob, size, actual_prob, actual, L, results=False):
+    """The verdict on a list decode's native outputs (pcub_ir_classify): info [L, K, B] u8, prob [L, B],
+    size [B], actual_prob [B], actual [K, B] -> the ten counters [trials, bad keys, bad symbols, sum of
+    list sizes, six outcome counts], and the outcome codes [B] (numpy u8) when asked."""
+    from . import _lib
+    B, K = int(size.shape[0]), int(actual.shape[0])
+    dev = size.device
+    counters = torch.zeros(10, dtype=torch.int64, device=dev)
+    res = torch.empty(max(1, B), dtype=torch.uint8, device=dev) if results else None
+    info = info.contiguous() if K else None
+    _lib.check(_lib.lib().pcub_ir_classify(sc._p(info), sc._p(prob.contiguous()), sc._p(size.contiguous()),
+                                           sc._p(actual_prob.contiguous()), sc._p(actual.contiguous()) if K else None,
+                                           B, int(L), K, sc._p(counters), sc._p(res), sc._stream()),
+               "pcub_ir_classify")
+    out = [int(v) for v in counters.tolist()]
+    return (out, res[:B].cpu().numpy()) if results else out
+
+
+def ir_workspace_bytes(code, L, chunk):
+    """(full, least) workspace of pcub_mc_run_ir at this chunk: the chunk's buffers with the list
+    decoder's whole slab, and with one workgroup's slots only."""
+    from . import _lib
+    lib = _lib.lib()
+    full = int(lib.pcub_mc_run_ir_workspace(int(chunk), code.q, code.n, int(L), code.K))
+    if full == 0:
+        raise ValueError("pcub_mc_run_ir: no pipeline for q=%d N=%d L=%d" % (code.q, code.N, L))
+    slab = (int(lib.pcub_scl_qary_workspace(int(chunk), code.q, code.n, int(L), code.K)) + 255) & ~255
+    return full, full - slab + int(lib.pcub_scl_qary_workspace(1, code.q, code.n, int(L), code.K))
+
+
+def run_ir(code, seed, offset, count, p, L, use_log=False, chunk=None, results=False, max_workspace_bytes=None):
+    """irSimulation's QSC trial loop as one device pipeline (pcub_mc_run_ir: pcub_ir_prepare, the list
+    decoder with the actual path, pcub_ir_classify) over global codewords [offset, offset + count);
+    returns the ten counters [trials, bad keys, bad symbols, sum of list sizes, six ProbResult counts],
+    and with results=True also the per-trial ProbResult codes (numpy u8 [count]).  The workspace is
+    the full size capped at max_workspace_bytes (default: half the free device memory), as
+    QaryListDecoder.decode_native caps its slab; the default chunk keeps the chunk's buffers (the
+    final lists, L K bytes a codeword, dominate) within half of that cap."""
+    from . import _lib
+    lib = _lib.lib()
+    dev = code.device
+    count, L = int(count), int(L)
+    cap = torch.cuda.mem_get_info(dev)[0] // 2 if max_workspace_bytes is None else int(max_workspace_bytes)
+    if chunk is None:
+        per_cw = L * (max(1, code.K) + 8) + code.N * (3 + 8 * code.q) + 12
+        chunk = min(1 << 16, (cap // 2) // per_cw)
+    chunk = int(max(1, min(chunk, count)))
+    full, least = ir_workspace_bytes(code, L, chunk)
+    ws = torch.empty(min(full, max(least, cap)), dtype=torch.uint8, device=dev)
+    counters = torch.zeros(10, dtype=torch.int64, device=dev)
+    res = torch.empty(max(1, count), dtype=torch.uint8, device=dev) if results else None
+    _lib.check(lib.pcub_mc_run_ir(int(seed), int(offset), count, code.n, code.q, float(p), L, 1 if use_log else 0,
+                                  sc._p(code.frozen_dev), code.K, chunk, sc._p(counters), sc._p(res), sc._p(ws),
+                                  ws.numel(), sc._stream()), "pcub_mc_run_ir")
+    out = [int(v) for v in counters.tolist()]
+    return (out, res[:count].cpu().numpy()) if results else out
+
+
 def philox_qsc_batch(code, seed, offset, B, p, tile=0):
     """q-ary information [K, B] u8 and QSC(p) joint rows [N, B, q] for global codewords
     [offset, offset + B) (pcub_mc_info_qary -> pcub_polar_encode_qary -> pcub_mc_channel_qsc);
