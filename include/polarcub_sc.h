@@ -15,6 +15,9 @@
  *                        QaryMemorylessVectorDistribution (:26-118).
  *   pcub_polar_encode_bin replaces BinaryPolarEncoderDecoder.encode
  *                        (BinaryPolarEncoderDecoder.py:46-69) for a uniform prior.
+ *   pcub_mc_run_bin / _qary / _deletion / _ir and pcub_mc_genie_deletion replace the trial loops
+ *                        (encodeDecodeSimulation, irSimulation, genieEncodeDecodeSimulation with
+ *                        the untrusted statistic) as device pipelines ending in integer counters.
  *   pcub_pack_bits / pcub_unpack_bits / pcub_transpose_pairs: layout helpers.
  *
  * Conventions
@@ -388,6 +391,38 @@ size_t pcub_mc_run_ir_workspace(int64_t chunk, int32_t q, int32_t log2N, int32_t
 int pcub_mc_run_ir(uint64_t seed, int64_t offset, int64_t count, int32_t log2N, int32_t q, double p, int32_t L,
                    int32_t use_log, const uint8_t* frozen, int32_t K, int64_t chunk, uint64_t* counters,
                    uint8_t* results, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Genie construction over the deletion channel as one device pipeline (genieEncodeDecodeSimulation,
+ * BinaryPolarEncoderDecoder.py:390-491, with the statistic of trustXYProbs = False, :159-171 --
+ * main_deletion's genie whenever n > n0), for global trials under the same (seed, g) keying as above.
+ *   pcub_genie_count  the statistic of one batch of exported leaves.
+ *       leaf      [N][B] f64 compact leaves as pcub_sc_leaf_bin / pcub_sc_leaf_deletion write them
+ *                 (+r = (1, r), -r = (r, 1), -0.0 = (0, 1), NaN = (0, 0); r in [0, 1])
+ *       u_words   [ceil(N/32)][B] the true bits (the frozen_val_cw layout)
+ *       counters  device u64[1 + 2N], accumulating, the caller zeroes them:
+ *                 [0] += B, [1 + i] += codewords wrong at position i, [1 + N + i] += ties at i.
+ *     With the marginals m of pcub_leaf_marginals ((0.5, 0.5) for the (0, 0) leaf) and the true bit u
+ *     a leaf is correct if m[u] > m[1 - u], a tie if they are equal, wrong otherwise; a trial adds
+ *     0 / 0.5 / 1 to Pe[i], so Pe[i] = (2 wrong[i] + tie[i]) / (2 trials).  Integer sums only: the
+ *     counters do not depend on scheduling.  log2N in 1..24; B = 0 is a no-op.  The statistic does
+ *     not depend on the channel the leaves came from.
+ *   pcub_mc_genie_deletion  for trials [offset, offset + count), chunk at a time on the stream, no
+ *     host synchronisation: u = pcub_mc_info (K = N) -> pcub_polar_encode_bin (no frozen position)
+ *     -> pcub_mc_deletion (template tmpl of W entries, channel pd) -> pcub_sc_leaf_deletion (stride
+ *     W, every position frozen to the trial's u, trellises built with the same pd) ->
+ *     pcub_genie_count.  Trial t's u and received word are those of the rate-1 code under
+ *     pcub_mc_info / pcub_mc_deletion at the same (seed, offset).  Workspace:
+ *     pcub_mc_genie_deletion_workspace(chunk, n, W) bytes (u, x, rx, rx_len, the [N][chunk] leaves --
+ *     8 N bytes a trial -- and the two constant masks; 0 for arguments it cannot size).
+ *     PCUB_EINVAL before any launch: a shape pcub_sc_leaf_deletion_supported refuses (n0 = 5
+ *     included), NULL counters / tmpl / workspace, W <= 0, pd outside [0, 1], negative count or
+ *     offset, chunk <= 0, a workspace that is too small. */
+int pcub_genie_count(const double* leaf, const uint32_t* u_words, int64_t B, int32_t log2N, uint64_t* counters,
+                     void* stream);
+size_t pcub_mc_genie_deletion_workspace(int64_t chunk, int32_t n, int32_t W);
+int pcub_mc_genie_deletion(uint64_t seed, int64_t offset, int64_t count, int32_t n, int32_t n0, const int32_t* tmpl,
+                           int32_t W, int32_t ones, double pd, int64_t chunk, uint64_t* counters, void* workspace,
+                           size_t workspace_bytes, void* stream);
 
 /* [B][nbits] u8 (0/1) -> ceil(nbits/32) x B words, and back. */
 int pcub_pack_bits(const uint8_t* bits, int64_t B, int32_t nbits, uint32_t* words, void* stream);

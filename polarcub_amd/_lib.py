@@ -199,6 +199,13 @@ def lib():
     L.pcub_mc_run_ir.restype = ctypes.c_int
     L.pcub_mc_run_ir.argtypes = [_u64, _i64, _i64, _i32, _i32, ctypes.c_double, _i32, _i32, _c_void_p, _i32, _i64,
                                  _c_void_p, _c_void_p, _c_void_p, ctypes.c_size_t, _c_void_p]
+    L.pcub_genie_count.restype = ctypes.c_int
+    L.pcub_genie_count.argtypes = [_c_void_p, _c_void_p, _i64, _i32, _c_void_p, _c_void_p]
+    L.pcub_mc_genie_deletion_workspace.restype = ctypes.c_size_t
+    L.pcub_mc_genie_deletion_workspace.argtypes = [_i64, _i32, _i32]
+    L.pcub_mc_genie_deletion.restype = ctypes.c_int
+    L.pcub_mc_genie_deletion.argtypes = [_u64, _i64, _i64, _i32, _i32, _c_void_p, _i32, _i32, ctypes.c_double, _i64,
+                                         _c_void_p, _c_void_p, ctypes.c_size_t, _c_void_p]
     if L.pcub_abi_version() != ABI_VERSION:
         raise ImportError("libpolarcub_hip.so ABI mismatch; rebuild with python -m polarcub_amd.build --force")
     _lib = L
@@ -220,7 +227,8 @@ EXPORTS = ["pcub_abi_version", "pcub_sc_decode_bin_workspace", "pcub_sc_decode_b
            "pcub_sc_decode_bin_compact_tiled", "pcub_mc_channel_tiled", "pcub_mc_channel_norm_tiled",
            "pcub_mc_channel_qsc_tiled", "pcub_sc_qary_tile", "pcub_sc_decode_qary_tiled",
            "pcub_mc_run_qary_workspace", "pcub_mc_run_qary", "pcub_mc_run_deletion_workspace", "pcub_mc_run_deletion",
-           "pcub_ir_prepare", "pcub_ir_classify", "pcub_mc_run_ir_workspace", "pcub_mc_run_ir"]
+           "pcub_ir_prepare", "pcub_ir_classify", "pcub_mc_run_ir_workspace", "pcub_mc_run_ir",
+           "pcub_genie_count", "pcub_mc_genie_deletion_workspace", "pcub_mc_genie_deletion"]
 
 
 def check(rc, what):

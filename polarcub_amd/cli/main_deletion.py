@@ -5,6 +5,10 @@ genie construction and encode/decode trials run through the GPU kernels
 (pcub_sc_leaf_deletion / pcub_sc_decode_deletion) whenever the shape is supported.
 
     python -m polarcub_amd.cli.main_deletion -n 8 -g 8000 -e 8000 -f frozen.txt
+
+--device-genie (not a flag of the reference) runs the -g trials as one device pipeline
+(coding.genieEncodeDecodeSimulationDevice): Philox draws keyed by the genie seed and the trial
+index instead of the reference's MT19937 streams.
 """
 import argparse
 import random
@@ -75,6 +79,10 @@ def parser():
                          "run. Default is 300.")
     ap.add_argument("-is", "--information-seed", type=int, default=400,
                     help="Seed for picking the random bits to encode. Default is 400.")
+    ap.add_argument("--device-genie", action="store_true",
+                    help="With -g: run the genie trials as one device pipeline (needs n > n0). The trials are "
+                         "drawn on the device from the genie seed (Philox), so they are other trials of the same "
+                         "law than the default's. Off by default.")
     return ap
 
 
@@ -101,9 +109,13 @@ def main(argv=None):
     frozenSet = None
     if G is not None:
         print("performing", G, "genie encoding/decoding trials to find a frozen set with WER at most", bound)
-        frozenSet = coding.genieEncodeDecodeSimulation(N, make_x, make_codeword, channel, make_xy, G, bound,
-                                                       genieSeed=args["genie_seed"], trustXYProbs=(n <= n0),
-                                                       filename=filename)
+        if args["device_genie"]:
+            frozenSet = coding.genieEncodeDecodeSimulationDevice(n, n0, xi, pd, G, bound, args["genie_seed"],
+                                                                 ones=ones, filename=filename)
+        else:
+            frozenSet = coding.genieEncodeDecodeSimulation(N, make_x, make_codeword, channel, make_xy, G, bound,
+                                                           genieSeed=args["genie_seed"], trustXYProbs=(n <= n0),
+                                                           filename=filename)
     if E is not None:
         if filename is not None:
             frozenSet = coding.read_frozen_file(filename)

@@ -562,6 +562,63 @@ def _device_genie_deletion(length, shape, words, U):
     return out
 
 
+def genie_pe_from_counts(trials, wrong, tie):
+    """Pe of the untrusted genie statistic from its integer counts: a wrong trial adds 1 and a tie 0.5
+    (BinaryPolarEncoderDecoder.py:159-171), so Pe[i] = (2 wrong[i] + tie[i]) / (2 trials)."""
+    return [(2 * int(w) + int(t)) / (2 * int(trials)) for w, t in zip(wrong, tie)]
+
+
+def genieEncodeDecodeSimulationDevice(n, n0, xi, pd, numberOfTrials, errorUpperBoundForFrozenSet, genieSeed, ones=0,
+                                      filename=None):
+    """genieEncodeDecodeSimulation over the deletion channel as one device pipeline
+    (mc.run_genie_deletion: the draws, the guard bands, the channel, the export decode and the
+    statistic all stay on the GPU; only 2N + 1 integer counters come back).  Returns the frozen set,
+    prints the reference's `pevec`, `code rate` and `codeword length` lines and optionally writes the
+    frozen-bits file in the reference's format.
+
+    It needs n > n0: main_deletion then runs the genie with trustXYProbs = False, and a trial adds
+    0, 0.5 or 1 to Pe[i] (the marginal at the true u_i larger than, equal to, smaller than the other
+    one) while TV is 0 under the uniform prior.  The TV and H lines are not printed (under the
+    uniform prior they are constants).
+
+    One difference from genieEncodeDecodeSimulation: u and the channel are drawn from Philox4x32-10
+    streams keyed by (genieSeed, trial index) instead of the reference's MT19937 streams, so the
+    trials are different trials of the same law (uniform u, the deletion channel with probability
+    pd), not the reference's trials.  Under torch.distributed each rank runs its slice of
+    [0, numberOfTrials) (mc.shard_range) and the counters are summed (mc.reduce_counters): the sum
+    does not depend on the number of ranks."""
+    import torch
+    import torch.distributed as dist
+
+    from . import channel, mc
+    if not n > n0:
+        raise ValueError("the device genie counts the untrusted statistic: it needs n > n0")
+    length = 1 << n
+    world, rank = 1, 0
+    device = torch.device("cuda")
+    if dist.is_available() and dist.is_initialized():
+        world, rank = dist.get_world_size(), dist.get_rank()
+        device = torch.device("cuda", torch.cuda.current_device())
+    lo, hi = mc.shard_range(numberOfTrials, rank, world)
+    trials, wrong, tie = mc.run_genie_deletion(n, n0, xi, pd, genieSeed, lo, hi - lo, ones=ones, device=device)
+    if world > 1:
+        backend_dev = device if dist.get_backend() == "nccl" else None
+        summed, _ = mc.reduce_counters([trials] + wrong.tolist() + tie.tolist(), 0.0, device=backend_dev)
+        trials, wrong, tie = summed[0], summed[1:1 + length], summed[1 + length:]
+    if trials != numberOfTrials:
+        raise RuntimeError("genie pipeline counted %d trials, expected %d" % (trials, numberOfTrials))
+    TV = [0.0] * length
+    Pe = genie_pe_from_counts(trials, wrong, tie)
+    print("pevec = ", Pe)
+    frozenSet = frozenSetFromTVAndPe(TV, Pe, errorUpperBoundForFrozenSet)
+    codewordLength = channel.guard_band_positions(n, n0, xi, ones)[1]
+    print("code rate = ", (length - len(frozenSet)) / codewordLength)
+    print("codeword length = ", codewordLength)
+    if filename is not None:
+        write_frozen_file(filename, frozenSet, numberOfTrials, TV, Pe)
+    return frozenSet
+
+
 def write_frozen_file(filename, frozenSet, numberOfTrials, TVvec, Pevec, argv=None):
     """Frozen-set file format of BinaryPolarEncoderDecoder.py:471-489."""
     with open(filename, "w") as f:

@@ -220,6 +220,68 @@ def run_deletion(code, seed, offset, count, n0, xi, pd, ones=0, table=None, chun
     return [int(v) for v in counters.tolist()]
 
 
+def genie_count(leaf, u_words, N):
+    """The genie's untrusted statistic of one batch (pcub_genie_count): compact leaves [N, B] f64 and
+    the true bits u_words [ceil(N/32), B] int32 -> (trials, wrong int64[N], tie int64[N]) as numpy:
+    position i of a codeword is wrong when the marginal at its true bit is the smaller one, a tie when
+    the two are equal (coding._genie_stats with trustXYProbs = False)."""
+    from . import _lib
+    N = int(N)
+    n = N.bit_length() - 1
+    if N < 2 or (1 << n) != N:
+        raise ValueError("N must be a power of two, at least 2")
+    B = int(leaf.shape[1])
+    if tuple(leaf.shape) != (N, B) or leaf.dtype != torch.float64 or tuple(u_words.shape) != ((N + 31) // 32, B) \
+            or u_words.dtype != torch.int32:
+        raise ValueError("leaf must be [N, B] float64 and u_words [ceil(N/32), B] int32")
+    counters = torch.zeros(1 + 2 * N, dtype=torch.int64, device=leaf.device)
+    _lib.check(_lib.lib().pcub_genie_count(sc._p(leaf.contiguous()), sc._p(u_words.contiguous()), B, n,
+                                           sc._p(counters), sc._stream()), "pcub_genie_count")
+    c = counters.cpu().numpy()
+    return int(c[0]), c[1:1 + N].copy(), c[1 + N:].copy()
+
+
+def genie_default_chunk(n, W):
+    """Trials a chunk of run_genie_deletion by default: a trial's buffers (8 N bytes of leaves, u, x, the
+    received row of W symbols and its length) and an eighth more for their alignment within
+    coding._GENIE_DEVICE_BYTES."""
+    from . import coding
+    N = 1 << int(n)
+    per_trial = 8 * N + 8 * ((N + 31) // 32) + int(W) + 4
+    return max(1, coding._GENIE_DEVICE_BYTES // (per_trial + per_trial // 8))
+
+
+def run_genie_deletion(n, n0, xi, pd, seed, offset, count, ones=0, chunk=None, device=None):
+    """The deletion channel's genie construction as one device pipeline (pcub_mc_genie_deletion: the
+    philox_deletion_batch generators of the rate-1 code, the export decode with every position frozen
+    to the trial's u, pcub_genie_count) over global trials [offset, offset + count); returns
+    (trials, wrong int64[N], tie int64[N]) as numpy.  The default chunk keeps the workspace (8 N
+    bytes of leaves a trial, mostly) within coding._GENIE_DEVICE_BYTES."""
+    from . import _lib
+    L = _lib.lib()
+    n, n0, ones, count = int(n), int(n0), int(ones), int(count)
+    N = 1 << n
+    dev = torch.device("cuda" if device is None else device)
+    if not L.pcub_sc_leaf_deletion_supported(n, n0, ones):
+        raise ValueError("no leaf-export deletion kernel for n=%d, n0=%d, ones=%d" % (n, n0, ones))
+    t = guard_template(n, n0, xi, ones, dev)
+    W = int(t.numel())
+    if chunk is None:
+        chunk = genie_default_chunk(n, W)
+    chunk = int(max(1, min(chunk, count)))
+    need = int(L.pcub_mc_genie_deletion_workspace(chunk, n, W))
+    if need == 0:
+        raise ValueError("pcub_mc_genie_deletion: no workspace for chunk=%d n=%d W=%d" % (chunk, n, W))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    counters = torch.zeros(1 + 2 * N, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.pcub_mc_genie_deletion(int(seed), int(offset), count, n, n0, sc._p(t), W, ones, float(pd), chunk,
+                                            sc._p(counters), sc._p(ws), ws.numel(), sc._stream()),
+                   "pcub_mc_genie_deletion")
+        c = counters.cpu().numpy()
+    return int(c[0]), c[1:1 + N].copy(), c[1 + N:].copy()
+
+
 def ir_prepare(code, seed, offset, B, p, use_log=False):
     """One IR trial's inputs for global codewords [offset, offset + B) (pcub_ir_prepare): the drawn
     word a [N, B] u8, its QSC(p) rows xy [N, B, q] f64 (their logarithms with use_log), and
