@@ -83,6 +83,22 @@ int pcub_sc_decode_bin_tiled(const double* xy, int64_t B, int32_t log2N, int32_t
                              const uint32_t* frozen_val, int32_t K, uint32_t* info_words, uint32_t* xhat_words,
                              uint32_t* u_words, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same decode reading the caller's per-codeword rows in place: xy [B][N][2] f64 (the reference's
+ * probs[i][x], one block of N rows a codeword), codeword b's row i at b N + i.  No staging pass and no
+ * second buffer: the generic kernels read it as the tiled layout of width 1, and the kernels the
+ * launcher picks by default at N = 1024 .. 16384 have rows twins that address a wave's 64 / G
+ * codewords -- still one contiguous block -- from a uniform base (pcub_sc_set_tiled_root(0) switches
+ * the twins off, as it does the tiled ones).  Outputs, workspace (pcub_sc_decode_bin_workspace) and
+ * error rules are pcub_sc_decode_bin_tiled's; identical decisions. */
+int pcub_sc_decode_bin_rows(const double* xy, int64_t B, int32_t log2N, const uint32_t* frozen_mask,
+                            const uint32_t* frozen_val, int32_t K, uint32_t* info_words, uint32_t* xhat_words,
+                            uint32_t* u_words, void* workspace, size_t workspace_bytes, void* stream);
+/* 1 where pcub_sc_decode_bin_rows is also the faster way to decode [B][N][2] rows (N <= 64 and
+ * N = 512 .. 16384 with the default variants), 0 where staging them with pcub_tile_pairs into
+ * pcub_sc_decode_bin_tiled still is (the generic kernels whose root loads are non-temporal: N = 128,
+ * 256 and N >= 32768); the facade and the torch operators follow it.  PCUB_EINVAL for a bad log2N. */
+int pcub_sc_bin_rows_preferred(int32_t log2N);
+
 /* q-ary SC decode (linear domain), 2 <= q <= 8, N >= 4.
  *   xy        [N][B][q] f64 joint probabilities P(X_i = x, Y_i = y_i)
  *   frozen    [N] u8 (1 = frozen; frozen symbols are 0, QaryPolarEncoderDecoder.py:351)
@@ -98,6 +114,12 @@ int pcub_sc_qary_tile(int32_t q, int32_t log2N);
 int pcub_sc_decode_qary_tiled(const double* xy, int64_t B, int32_t log2N, int32_t q, int32_t tile,
                               const uint8_t* frozen, int32_t K, uint8_t* info, uint8_t* xhat, void* workspace,
                               size_t workspace_bytes, void* stream);
+
+/* ... reading the caller's per-codeword rows in place: xy [B][N][q] f64, codeword b's row i at b N + i
+ * (pcub_sc_decode_bin_rows' layout; workspace pcub_sc_decode_qary_workspace; the q = 4 split-level
+ * kernel has a rows twin, pcub_sc_set_qary_tiled_root(0) switches it off). */
+int pcub_sc_decode_qary_rows(const double* xy, int64_t B, int32_t log2N, int32_t q, const uint8_t* frozen, int32_t K,
+                             uint8_t* info, uint8_t* xhat, void* workspace, size_t workspace_bytes, void* stream);
 
 /* q-ary polar encoder (QaryPolarEncoderDecoder.py:65-88, frozen symbols 0):
  *   info [K][B] u8 -> x [N][B] u8, combine x[2h] = (xm+xp)%q, x[2h+1] = (q-xp)%q. */

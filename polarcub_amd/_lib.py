@@ -138,6 +138,14 @@ def lib():
     L.pcub_sc_decode_bin_tiled.restype = ctypes.c_int
     L.pcub_sc_decode_bin_tiled.argtypes = [_c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p,
                                            _c_void_p, _c_void_p, ctypes.c_size_t, _c_void_p]
+    L.pcub_sc_decode_bin_rows.restype = ctypes.c_int
+    L.pcub_sc_decode_bin_rows.argtypes = [_c_void_p, _i64, _i32, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p,
+                                          _c_void_p, _c_void_p, ctypes.c_size_t, _c_void_p]
+    L.pcub_sc_bin_rows_preferred.restype = ctypes.c_int
+    L.pcub_sc_bin_rows_preferred.argtypes = [_i32]
+    L.pcub_sc_decode_qary_rows.restype = ctypes.c_int
+    L.pcub_sc_decode_qary_rows.argtypes = [_c_void_p, _i64, _i32, _i32, _c_void_p, _i32, _c_void_p, _c_void_p,
+                                           _c_void_p, ctypes.c_size_t, _c_void_p]
     L.pcub_sc_decode_bin_compact_tiled.restype = ctypes.c_int
     L.pcub_sc_decode_bin_compact_tiled.argtypes = [_c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p, _i32, _c_void_p,
                                                    _c_void_p, _c_void_p, _c_void_p, ctypes.c_size_t, _c_void_p]
@@ -228,7 +236,8 @@ EXPORTS = ["pcub_abi_version", "pcub_sc_decode_bin_workspace", "pcub_sc_decode_b
            "pcub_mc_channel_qsc_tiled", "pcub_sc_qary_tile", "pcub_sc_decode_qary_tiled",
            "pcub_mc_run_qary_workspace", "pcub_mc_run_qary", "pcub_mc_run_deletion_workspace", "pcub_mc_run_deletion",
            "pcub_ir_prepare", "pcub_ir_classify", "pcub_mc_run_ir_workspace", "pcub_mc_run_ir",
-           "pcub_genie_count", "pcub_mc_genie_deletion_workspace", "pcub_mc_genie_deletion"]
+           "pcub_genie_count", "pcub_mc_genie_deletion_workspace", "pcub_mc_genie_deletion",
+           "pcub_sc_decode_bin_rows", "pcub_sc_decode_qary_rows", "pcub_sc_bin_rows_preferred"]
 
 
 def check(rc, what):

@@ -28,13 +28,13 @@ ARCH = os.environ.get("PCUB_ARCH", "gfx950")
 
 SOURCES = ["sc_del_w4.hip", "sc_del_w5.hip", "sc_del_dense.hip", "sc_del_n4w.hip", "sc_del_n4wx.hip", "sc_del_n4.hip", "sc_del_n4o.hip", "sc_del_n4x.hip", "sc_del_n3.hip", "sc_del_n3o.hip", "sc_del_n3x.hip",
            "sc_del_n2.hip", "sc_del_n2o.hip", "sc_del_n2x.hip", "sc_del_n1.hip", "sc_del_n1o.hip", "sc_del_n1x.hip",
-           "sc_bin.hip", "sc_bin_k0.hip", "sc_bin_k1.hip", "sc_bin_k2.hip", "sc_bin_k4.hip", "sc_bin_k5.hip", "sc_bin_k6.hip", "sc_bin_k7.hip", "sc_bin_k8.hip", "sc_bin_k9.hip", "sc_qary.hip",
-           "sc_qary_q2.hip", "sc_qary_q3.hip", "sc_qary_q4.hip", "sc_qary_q56.hip", "sc_qary_q78.hip",
+           "sc_bin.hip", "sc_bin_k0.hip", "sc_bin_k1.hip", "sc_bin_k2.hip", "sc_bin_k4.hip", "sc_bin_k5.hip", "sc_bin_k6.hip", "sc_bin_k7.hip", "sc_bin_k8.hip", "sc_bin_k9.hip", "sc_bin_k10.hip", "sc_bin_k11.hip", "sc_qary.hip",
+           "sc_qary_q2.hip", "sc_qary_q3.hip", "sc_qary_q4.hip", "sc_qary_q4r.hip", "sc_qary_q56.hip", "sc_qary_q78.hip",
            "sc_util.hip", "sc_del.hip", "sc_leaf.hip", "sc_qary_log.hip", "scl.hip", "scl_wg.hip",
            "sc_mc.hip", "sc_ir.hip", "sc_genie.hip"]
 # compile order only (the link order is SOURCES'): the units that take minutes each, longest first
-SLOWEST_FIRST = ["sc_bin_k9.hip", "sc_bin_k6.hip", "sc_qary_q4.hip", "sc_qary_q78.hip", "sc_bin_k8.hip",
-                 "sc_qary_q56.hip", "sc_bin_k7.hip", "sc_del_n4o.hip", "sc_del_n4x.hip", "sc_qary_q3.hip"]
+SLOWEST_FIRST = ["sc_bin_k9.hip", "sc_bin_k6.hip", "sc_bin_k11.hip", "sc_qary_q4.hip", "sc_qary_q78.hip", "sc_bin_k8.hip",
+                 "sc_qary_q56.hip", "sc_bin_k10.hip", "sc_bin_k7.hip", "sc_qary_q4r.hip", "sc_del_n4o.hip", "sc_del_n4x.hip", "sc_qary_q3.hip"]
 CFLAGS = ["--offload-arch=" + ARCH, "-O3", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-std=c++17", "-Wall",
           "-Wno-unused-function"]
 

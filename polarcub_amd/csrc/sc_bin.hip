@@ -87,6 +87,7 @@ KernFn variant_kernel(int v) {
 constexpr int kDefaultVariant = 26;
 int g_variant = kDefaultVariant;
 int g_tiled_root = 1;  // pcub_sc_set_tiled_root
+int g_rows_nt = 0;     // pcub_sc_set_rows_nt: the rows twins' root loads non-temporal where both forms are built
 int g_max_blocks = 0;  // workgroups per CU cap (0 = as many as fit)
 constexpr size_t kLdsPerCu = 160 * 1024;
 
@@ -217,6 +218,14 @@ extern "C" int pcub_sc_set_tiled_root(int on) {
     g_tiled_root = on ? 1 : 0;
     return old;
 }
+// Tuning hook (not part of the stable ABI): the rows twins (pcub_sc_decode_bin_rows) load their root
+// plainly (0, the default) or non-temporally (1) where both kernels are built (variant 26); returns the
+// previous setting.  Identical outputs.
+extern "C" int pcub_sc_set_rows_nt(int on) {
+    const int old = g_rows_nt;
+    g_rows_nt = on ? 1 : 0;
+    return old;
+}
 // the variant a decode of code length 2^log2N launches (the selected one, or its fallback)
 extern "C" int pcub_sc_variant_for(int32_t log2N) {
     if (log2N < 6 || log2N > 24) return PCUB_EINVAL;
@@ -238,10 +247,27 @@ extern "C" size_t pcub_sc_decode_bin_workspace(int64_t B, int32_t log2N) {
 
 namespace {
 
+BinKernFn rows_twin(int v, bool nt) {
+    if (BinKernFn k = bin_kernel_rows(v, nt)) return k;
+    return bin_kernel_rows2(v, nt);
+}
+
+// Where reading [B][N] rows in place beats staging them through pcub_tile_pairs (scripts/ab_api_layout.py,
+// DESIGN.md 3.1): the small-code kernels, the variants with a rows twin, and the generic kernels whose
+// root loads are plain (variant 0, 1).  The other generic kernels load their root non-temporally, which
+// the rows layout's partial-line accesses pay for (N = 256, variant 24: 8.5 ms against 5.7 ms staged).
+bool rows_preferred(int n) {
+    if (n <= 5) return true;
+    const int v = pick_variant(n);
+    if (g_tiled_root && (rows_twin(v, false) || rows_twin(v, true))) return true;
+    return kVar[v].T == 0;
+}
+
 // raw pairs xy, or compact rows xc through a variant's compact-root twin (the caller checks one exists)
 int decode_bin_impl(const double* xy, const double* xc, int64_t B, int32_t log2N, int32_t tile,
                     const uint32_t* frozen_mask, const uint32_t* frozen_val, int32_t K, uint32_t* info_words,
-                    uint32_t* xhat_words, uint32_t* u_words, void* workspace, size_t workspace_bytes, void* stream) {
+                    uint32_t* xhat_words, uint32_t* u_words, void* workspace, size_t workspace_bytes, void* stream,
+                    bool rows = false) {
     if (B < 0 || log2N < 0 || log2N > 24 || tile < 0 || tile > 4096 || !frozen_mask || !frozen_val) return PCUB_EINVAL;
     if (K < 0 || K > (1 << log2N) || (K > 0 && !info_words) || (B > 0 && !xy && !xc)) return PCUB_EINVAL;
     if (B == 0) return 0;
@@ -304,6 +330,12 @@ int decode_bin_impl(const double* xy, const double* xc, int64_t B, int32_t log2N
     if (g_experiment && tile == 64 / kVar[v].G) kern = exp_kernel(g_experiment, v, xc != nullptr);
     if (!kern && g_tiled_root && tile == 64 / kVar[v].G) kern = bin_kernel_tiled_root(v, xc != nullptr);
     if (!kern && g_tiled_root && tile == 64 / kVar[v].G) kern = bin_kernel_tiled_root2(v, xc != nullptr);
+    // the caller's [B][N] rows (tile == 1): the rows twin where one is instantiated and a wave's block of
+    // 64 / G codewords stays inside its 32-bit lane offsets
+    if (!kern && rows && g_tiled_root && !xc && ((64ull / kVar[v].G) << log2N) * sizeof(double2) < (1ull << 32)) {
+        kern = rows_twin(v, g_rows_nt != 0);
+        if (!kern) kern = rows_twin(v, g_rows_nt == 0);  // the other load form where only one is built
+    }
     if (!kern) kern = xc ? bin_kernel_compact(v) : variant_kernel(v);
     if (!kern) return PCUB_EINVAL;
     hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(kBlock), launch_lds(v, log2N), st, A);
@@ -353,6 +385,25 @@ extern "C" int pcub_sc_decode_bin_tiled(const double* xy, int64_t B, int32_t log
     if (!xy && B > 0) return PCUB_EINVAL;
     return decode_bin_impl(xy, nullptr, B, log2N, tile, frozen_mask, frozen_val, K, info_words, xhat_words, u_words,
                            workspace, workspace_bytes, stream);
+}
+
+// The caller's per-codeword rows xy [B][N][2] read in place: the tiled layout of width 1 for the generic
+// kernels (codeword cw's row 0 at element cw N, rows 1 element apart), and the rows twins of the
+// default variants (bin_kernel_rows) where they are built.  No staging pass, no second buffer.
+extern "C" int pcub_sc_decode_bin_rows(const double* xy, int64_t B, int32_t log2N, const uint32_t* frozen_mask,
+                                       const uint32_t* frozen_val, int32_t K, uint32_t* info_words,
+                                       uint32_t* xhat_words, uint32_t* u_words, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    if (!xy && B > 0) return PCUB_EINVAL;
+    return decode_bin_impl(xy, nullptr, B, log2N, 1, frozen_mask, frozen_val, K, info_words, xhat_words, u_words,
+                           workspace, workspace_bytes, stream, true);
+}
+
+// 1 when pcub_sc_decode_bin_rows is the faster way to decode [B][N][2] rows at 2^log2N, 0 when staging
+// them with pcub_tile_pairs into pcub_sc_decode_bin_tiled still is (the rows entry point works either way)
+extern "C" int pcub_sc_bin_rows_preferred(int32_t log2N) {
+    if (log2N < 0 || log2N > 24) return PCUB_EINVAL;
+    return rows_preferred(log2N) ? 1 : 0;
 }
 
 extern "C" int pcub_sc_decode_bin_compact_direct(int32_t log2N) {

@@ -50,7 +50,7 @@ inline size_t bin_ylds_bytes(int v, int n) {
 }
 
 template <int S, int G, int W, bool LDS, int NT, bool YL = false, bool HL = false, int PF = 0, bool CR = false,
-          bool TR = false>
+          bool TR = false, bool RW = false>
 __global__ __launch_bounds__(kBinBlock, W) void k_sc_bin(BinArgs A) {
     // [S pairs][kBinBlock] when LDS (HL: [S doubles][kBinBlock]), then [Nv/32 words][kBinBlock]
     // when YL (plus occupancy padding)
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(kBinBlock, W) void k_sc_bin(BinArgs A) {
     while (wt < nwt) {
         const long long cw = wt * CWW + lane / G;
         const bool valid = cw < A.B;
-        decode_codeword<S, G, LDS, NT, YL, HL, PF, CR, -1, TR>(A, valid ? cw : A.B - 1, j, lane, slot, valid, last,
+        decode_codeword<S, G, LDS, NT, YL, HL, PF, CR, -1, TR, RW>(A, valid ? cw : A.B - 1, j, lane, slot, valid, last,
                                                YL ? (uint32_t*)(lds_last + LDS2) + threadIdx.x : nullptr, kBinBlock,
                                                HL ? (double*)lds_last + threadIdx.x : nullptr);
         wt = A.wtiles ? next_wave_tile(A.wtiles, lane) : wt + (long long)gridDim.x * WPB;
@@ -97,5 +97,10 @@ BinKernFn bin_kernel_compact(int v);
 // 32-bit lane offsets), pairs or compact rows; nullptr where not instantiated (sc_bin_k7.hip)
 BinKernFn bin_kernel_tiled_root(int v, bool compact);
 BinKernFn bin_kernel_tiled_root2(int v, bool compact);  // sc_bin_k9.hip: the N >= 4096 variants' twins
+// variant v reading the caller's [B][N] rows in place (RW: a wave's 64 / G codewords are one block of
+// (64 / G) N rows; the same uniform base and 32-bit lane offsets as TR), or nullptr.  nt: the root
+// loads non-temporal as the tiled twins' (else plain; variant 26 has both, sc_bin_k10.hip)
+BinKernFn bin_kernel_rows(int v, bool nt);
+BinKernFn bin_kernel_rows2(int v, bool nt);  // sc_bin_k11.hip: variants 30, 33
 
 }  // namespace pcub

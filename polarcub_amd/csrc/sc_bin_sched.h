@@ -370,7 +370,7 @@ PCUB_HD void xhat_r5(uint32_t* a, uint32_t* out) {
 //     hl, second half in registers; hl_run), one stored stage depth fewer than the plain S
 // PF: prefetch distance of the final passes (column pairs whose loads are in flight ahead)
 template <int S, int G, bool LDS = false, int NT = 0, bool YL = false, bool HL = false, int PF = 0, bool CR = false,
-          int PF1 = -1, bool TR = false>
+          int PF1 = -1, bool TR = false, bool RW = false>
 PCUB_HD void decode_codeword(const BinArgs& A, long long cw, int j, int lane, long long slot, bool store,
                              Lvl last = Lvl{nullptr, 0}, uint32_t* ylds = nullptr, long long ystride = 0,
                              double* hl = nullptr) {
@@ -392,13 +392,22 @@ PCUB_HD void decode_codeword(const BinArgs& A, long long cw, int j, int lane, lo
     const int D = nv - s;
     const long long ns = A.nslots;
     const long long B = A.B;
-    const long long rs = root_stride(A);  // root row stride: B ([N][B] rows) or the tile width
+    const long long rs = RW ? 1LL : root_stride(A);  // root row stride: B ([N][B] rows) or the tile width
     // TR (tiled root, tile = the wave's 64 / G codewords): the wave's tile is one contiguous block,
     // its base wave-uniform (SGPRs) and this lane's rows a 32-bit byte offset into it, so a root load
     // is a global load with an SGPR base and a VGPR offset -- no 64-bit address add in the VALU.
     // Otherwise a per-lane pointer (64-bit adds per load).
+    // RW (with TR; the caller's [B][N] rows, A.tile == 1 so rs == 1): the wave's 64 / G codewords are
+    // still one contiguous block of (64 / G) N rows, codeword c of them at row c N of it -- the same
+    // uniform base, and the lane's offset (cw % (64 / G)) N + 2 bitrev(j) rows (the launcher checks
+    // that a wave's block stays below 2^32 bytes).
+    static_assert(!RW || (TR && !CR), "the rows twins: uniform base, raw pairs");
     long long tbase, lrow;
-    if constexpr (TR) {
+    if constexpr (TR && RW) {
+        constexpr int CWW = 64 / G;
+        tbase = uniform64((cw / CWW) * ((long long)CWW << n));
+        lrow = ((cw % CWW) << n) + 2 * (long long)bitrev((uint32_t)j, n - 1) * rs;
+    } else if constexpr (TR) {
         tbase = uniform64((cw / A.tile) * ((long long)A.tile << n));
         lrow = cw % A.tile + 2 * (long long)bitrev((uint32_t)j, n - 1) * rs;
     } else {

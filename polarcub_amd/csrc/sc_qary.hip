@@ -190,7 +190,8 @@ extern "C" size_t pcub_sc_decode_qary_workspace(int64_t B, int32_t log2N, int32_
 namespace {
 
 int decode_qary_impl(const double* xy, int64_t B, int32_t log2N, int32_t q, int32_t tile, const uint8_t* frozen,
-                     int32_t K, uint8_t* info, uint8_t* xhat, void* workspace, size_t workspace_bytes, void* stream) {
+                     int32_t K, uint8_t* info, uint8_t* xhat, void* workspace, size_t workspace_bytes, void* stream,
+                     bool rows = false) {
     if (B < 0 || log2N < 2 || log2N > 20 || !qkernel(q, log2N) || !frozen || tile < 0 || tile > 4096) return PCUB_EINVAL;
     if (K < 0 || K > (1 << log2N) || (K > 0 && !info) || (B > 0 && !xy)) return PCUB_EINVAL;
     if (B == 0) return 0;
@@ -233,6 +234,12 @@ int decode_qary_impl(const double* xy, int64_t B, int32_t log2N, int32_t q, int3
     if (!kern && g_qtr && c.hl && tile == 64 / c.G && q == 4 && pcub_sc_fixed_n())
         kern = qary_kernel_q4_h_tr_n(c.S, c.G, log2N);
     if (!kern && g_qtr && c.hl && tile == 64 / c.G) kern = qary_kernel_h_tr(q, c.S, c.G);
+    // the caller's [B][N][q] rows (tile == 1): the rows twin where one is instantiated and a wave's block
+    // of 64 / G codewords stays inside its 32-bit lane offsets
+    if (!kern && rows && g_qtr && c.hl && q == 4 && ((64ull / c.G) << log2N) * q * sizeof(double) < (1ull << 32)) {
+        if (pcub_sc_fixed_n()) kern = qary_kernel_q4_h_rows_n(c.S, c.G, log2N);
+        if (!kern) kern = qary_kernel_q4_h_rows(c.S, c.G);
+    }
     if (!kern) kern = qkernel(q, log2N);
     hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(kQBlock), qlaunch_lds(q, log2N), st, A);
     return (int)hipGetLastError();
@@ -256,6 +263,14 @@ extern "C" int pcub_sc_decode_qary_tiled(const double* xy, int64_t B, int32_t lo
                                          const uint8_t* frozen, int32_t K, uint8_t* info, uint8_t* xhat,
                                          void* workspace, size_t workspace_bytes, void* stream) {
     return decode_qary_impl(xy, B, log2N, q, tile, frozen, K, info, xhat, workspace, workspace_bytes, stream);
+}
+
+// The caller's per-codeword rows xy [B][N][q] read in place: the tiled layout of width 1 for the generic
+// kernels, the rows twin of the q = 4 split-level kernel where it runs.  No staging pass.
+extern "C" int pcub_sc_decode_qary_rows(const double* xy, int64_t B, int32_t log2N, int32_t q, const uint8_t* frozen,
+                                        int32_t K, uint8_t* info, uint8_t* xhat, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+    return decode_qary_impl(xy, B, log2N, q, 1, frozen, K, info, xhat, workspace, workspace_bytes, stream, true);
 }
 
 extern "C" int pcub_polar_encode_qary(const uint8_t* info, int64_t B, int32_t log2N, int32_t q, const uint8_t* frozen,

@@ -539,7 +539,10 @@ PCUB_HD void q_final_dispatch(const QPass& P, QV<Q>* v, bool gop, bool root, dou
 // NC >= 0: the code length 2^NC is a compile-time constant (the kernel runs only at it), so the per-
 // position row offsets and level bases fold (binary decode_codeword's NC); TR kernels also know
 // their tile width, 64 / G.
-template <int Q, int S, int G = 1, int U = 1, bool YL = false, bool HL = false, bool TR = false, int NC = -1>
+// RW (with TR): the caller's [B][N][Q] rows read in place -- a wave's 64 / G codewords are one block of
+// (64 / G) N rows, codeword c of them at row c N, rows 1 apart (binary decode_codeword's RW).
+template <int Q, int S, int G = 1, int U = 1, bool YL = false, bool HL = false, bool TR = false, int NC = -1,
+          bool RW = false>
 PCUB_HD void decode_qary_cw(const QArgs& A, long long cw, long long slot, bool store, int j = 0, int lane = 0,
                             uint32_t* ylds = nullptr, long long ystride = 0, double* hl = nullptr) {
     constexpr int SR = HL ? 2 * S : S;  // positions per lane at the chain's last level
@@ -559,13 +562,18 @@ PCUB_HD void decode_qary_cw(const QArgs& A, long long cw, long long slot, bool s
     const long long ys = YL ? ystride : ns;  // symbol word stride
     // root rows of lane j: real position j + G*t is row bitrev_n(j) + bitrev_{nv}(t)
     // tiled layout: codeword cw's row 0 at ((cw / T) N) T + cw % T, rows T apart
-    const long long rs = TR ? 64 / G : A.tile > 0 ? (long long)A.tile : A.B;
+    static_assert(!RW || TR, "the rows twins address from a uniform base");
+    const long long rs = RW ? 1 : TR ? 64 / G : A.tile > 0 ? (long long)A.tile : A.B;
     const long long rb = A.tile > 0 ? (cw / rs) * (rs << n) + cw % rs : cw;
     // TR (tile = the wave's 64 / G codewords): the tile's base wave-uniform (SGPRs), this lane's rows
     // a 32-bit byte offset (binary decode_codeword's TR)
     const double* in;
     uint32_t lin = 0;
-    if constexpr (TR) {
+    if constexpr (TR && RW) {
+        constexpr long long CWW = 64 / G;
+        in = A.xy + uniform64((cw / CWW) * (CWW << n)) * Q;
+        lin = (uint32_t)((((cw % CWW) << n) + (long long)bitrev((uint32_t)j, n)) * Q * 8);
+    } else if constexpr (TR) {
         in = A.xy + uniform64((cw / rs) * (rs << n)) * Q;
         lin = (uint32_t)((cw % rs + (long long)bitrev((uint32_t)j, n) * rs) * Q * 8);
     } else {

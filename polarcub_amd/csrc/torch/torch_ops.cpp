@@ -92,7 +92,9 @@ void check_xy_bin(const at::Tensor& xy_in) {
                 "polarcub: xy must be a float64 [B, N, 2] device tensor");
 }
 
-// the tiled decode (the facade's and the bench's kernels) on packed device masks
+// the decode on packed device masks, reading the [B, N, 2] rows in place (pcub_sc_decode_bin_rows: the
+// facade's path; no staging pass, so the only allocations are the workspace and the outputs) wherever
+// pcub_sc_bin_rows_preferred says that is also the faster path, else through pcub_tile_pairs as before
 std::tuple<at::Tensor, at::Tensor> decode_bin_core(const at::Tensor& xy_in, const at::Tensor& fm_words,
                                                    const at::Tensor& fv_words, int64_t K) {
     const int64_t B = xy_in.size(0), N = xy_in.size(1);
@@ -101,22 +103,33 @@ std::tuple<at::Tensor, at::Tensor> decode_bin_core(const at::Tensor& xy_in, cons
     if (B == 0) return {at::empty({0, K}, u8), at::empty({0, N}, u8)};
     void* s = stream_of(xy_in);
     auto xy = xy_in.contiguous();
-    const int T = pcub_sc_bin_tile(n);
-    TORCH_CHECK(T > 0, "polarcub: no binary decode kernel for N=", N);
-    auto xt = at::empty({(B + T - 1) / T, N, T, 2}, xy.options());
-    check_rc(pcub_tile_pairs(xy.data_ptr<double>(), B, (int32_t)N, 2, T, xt.data_ptr<double>(), s), "pcub_tile_pairs");
     const size_t wsb = pcub_sc_decode_bin_workspace(B, n);
     auto ws = at::empty({(int64_t)std::max<size_t>(wsb, 16)}, u8);
     auto i32 = xy.options().dtype(at::kInt);
     auto iw = at::empty({std::max<int64_t>(1, (K + 31) / 32), B}, i32);
     auto xw = at::empty({(N + 31) / 32, B}, i32);
-    check_rc(pcub_sc_decode_bin_tiled(xt.data_ptr<double>(), B, n, T,
-                                      reinterpret_cast<const uint32_t*>(fm_words.data_ptr<int32_t>()),
-                                      reinterpret_cast<const uint32_t*>(fv_words.data_ptr<int32_t>()), (int32_t)K,
-                                      reinterpret_cast<uint32_t*>(iw.data_ptr<int32_t>()),
-                                      reinterpret_cast<uint32_t*>(xw.data_ptr<int32_t>()), nullptr, ws.data_ptr(),
-                                      (size_t)ws.numel(), s),
-             "pcub_sc_decode_bin_tiled");
+    if (pcub_sc_bin_rows_preferred(n) != 1) {
+        const int T = pcub_sc_bin_tile(n);
+        TORCH_CHECK(T > 0, "polarcub: no binary decode kernel for N=", N);
+        auto xt = at::empty({(B + T - 1) / T, N, T, 2}, xy.options());
+        check_rc(pcub_tile_pairs(xy.data_ptr<double>(), B, (int32_t)N, 2, T, xt.data_ptr<double>(), s),
+                 "pcub_tile_pairs");
+        check_rc(pcub_sc_decode_bin_tiled(xt.data_ptr<double>(), B, n, T,
+                                          reinterpret_cast<const uint32_t*>(fm_words.data_ptr<int32_t>()),
+                                          reinterpret_cast<const uint32_t*>(fv_words.data_ptr<int32_t>()), (int32_t)K,
+                                          reinterpret_cast<uint32_t*>(iw.data_ptr<int32_t>()),
+                                          reinterpret_cast<uint32_t*>(xw.data_ptr<int32_t>()), nullptr,
+                                          ws.data_ptr(), (size_t)ws.numel(), s),
+                 "pcub_sc_decode_bin_tiled");
+        return {unpack_words(iw, B, K, s), unpack_words(xw, B, N, s)};
+    }
+    check_rc(pcub_sc_decode_bin_rows(xy.data_ptr<double>(), B, n,
+                                     reinterpret_cast<const uint32_t*>(fm_words.data_ptr<int32_t>()),
+                                     reinterpret_cast<const uint32_t*>(fv_words.data_ptr<int32_t>()), (int32_t)K,
+                                     reinterpret_cast<uint32_t*>(iw.data_ptr<int32_t>()),
+                                     reinterpret_cast<uint32_t*>(xw.data_ptr<int32_t>()), nullptr, ws.data_ptr(),
+                                     (size_t)ws.numel(), s),
+             "pcub_sc_decode_bin_rows");
     return {unpack_words(iw, B, K, s), unpack_words(xw, B, N, s)};
 }
 
@@ -233,19 +246,15 @@ std::tuple<at::Tensor, at::Tensor> sc_decode_qary_f64(int64_t q, const at::Tenso
     if (B == 0) return {at::empty({0, K}, u8), at::empty({0, N}, u8)};
     void* s = stream_of(xy_in);
     auto xy = xy_in.contiguous();
-    const int T = pcub_sc_qary_tile((int32_t)q, n);
-    TORCH_CHECK(T > 0, "polarcub: no q-ary decode kernel for q=", q, ", N=", N);
-    auto xt = at::empty({(B + T - 1) / T, N, T, q}, xy.options());
-    check_rc(pcub_tile_pairs(xy.data_ptr<double>(), B, (int32_t)N, (int32_t)q, T, xt.data_ptr<double>(), s),
-             "pcub_tile_pairs");
+    TORCH_CHECK(pcub_sc_qary_tile((int32_t)q, n) > 0, "polarcub: no q-ary decode kernel for q=", q, ", N=", N);
     const size_t wsb = pcub_sc_decode_qary_workspace(B, n, (int32_t)q);
     auto ws = at::empty({(int64_t)std::max<size_t>(wsb, 16)}, u8);
     auto info = at::empty({std::max<int64_t>(1, K), B}, u8);
     auto xh = at::empty({N, B}, u8);
-    check_rc(pcub_sc_decode_qary_tiled(xt.data_ptr<double>(), B, n, (int32_t)q, T, fz.data_ptr<uint8_t>(), (int32_t)K,
-                                       info.data_ptr<uint8_t>(), xh.data_ptr<uint8_t>(), ws.data_ptr(),
-                                       (size_t)ws.numel(), s),
-             "pcub_sc_decode_qary_tiled");
+    check_rc(pcub_sc_decode_qary_rows(xy.data_ptr<double>(), B, n, (int32_t)q, fz.data_ptr<uint8_t>(), (int32_t)K,
+                                      info.data_ptr<uint8_t>(), xh.data_ptr<uint8_t>(), ws.data_ptr(),
+                                      (size_t)ws.numel(), s),
+             "pcub_sc_decode_qary_rows");
     return {info.narrow(0, 0, K).t().contiguous(), xh.t().contiguous()};
 }
 

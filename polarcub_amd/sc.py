@@ -6,7 +6,8 @@ tensors; every call is asynchronous on torch's current stream.
 
 Layouts (see include/polarcub_sc.h):
   * joint probabilities, native:  [N, B, 2] float64  (element-major, codeword-minor)
-  * joint probabilities, per-cw:  [B, N, 2] float64  (the reference's probs[i][x], stacked)
+  * joint probabilities, per-cw:  [B, N, 2] float64  (the reference's probs[i][x], stacked; the
+                                  decode() methods and decode_rows_native read it in place)
   * bit vectors, packed:          [ceil(nbits/32), B] int32 words (bit t of word w = bit 32w+t)
   * bit vectors, unpacked:        [B, nbits] uint8
 """
@@ -187,6 +188,12 @@ def bin_tile(n):
     return int(_lib.lib().pcub_sc_bin_tile(int(n)))
 
 
+def rows_preferred(n):
+    """True where decoding [B, N, 2] rows in place (BinaryDecoder.decode_rows_native) is also faster than
+    staging them through tile_pairs (pcub_sc_bin_rows_preferred)."""
+    return int(_lib.lib().pcub_sc_bin_rows_preferred(int(n))) == 1
+
+
 def tile_rows(native, T):
     """[N, B, ...] rows (codeword-minor) -> the tiled layout [ceil(B/T), N, T, ...] (zero-padded)."""
     N, B = native.shape[0], native.shape[1]
@@ -281,14 +288,41 @@ class BinaryDecoder:
         _lib.check(rc, "pcub_sc_decode_bin_compact")
         return info, xh, None
 
+    def decode_rows_native(self, xy, want_xhat=True, want_u=False, out=None):
+        """xy: [B, N, 2] float64 on device (per-codeword rows, as the reference's probs), read in place
+        (pcub_sc_decode_bin_rows): no staging pass and no second buffer.  The same decode as
+        decode_native on the transposed rows.  Returns packed (info_words, xhat_words|None, u_words|None)."""
+        c = self.code
+        if xy.dtype != torch.float64 or xy.dim() != 3 or xy.shape[1] != c.N or xy.shape[2] != 2:
+            raise ValueError("xy must be float64 [B, N, 2] with N=%d" % c.N)
+        if not xy.is_cuda:
+            raise ValueError("xy must be a device tensor")
+        xy = xy.contiguous()
+        B = xy.shape[0]
+        dev = xy.device
+        if out is None:
+            info = torch.empty((max(1, c.info_words), B), dtype=torch.int32, device=dev)
+            xh = torch.empty((c.n_words, B), dtype=torch.int32, device=dev) if want_xhat else None
+            uo = torch.empty((c.n_words, B), dtype=torch.int32, device=dev) if want_u else None
+        else:
+            info, xh, uo = out
+        ws = self.workspace(B)
+        rc = _lib.lib().pcub_sc_decode_bin_rows(_p(xy), B, c.n, _p(c.fmask_dev), _p(c.fval_dev), c.K, _p(info),
+                                                _p(xh), _p(uo), _p(ws), ws.numel(), _stream())
+        _lib.check(rc, "pcub_sc_decode_bin_rows")
+        return info, xh, uo
+
     def decode(self, xy):
         """xy: [B, N, 2] float64 (per-codeword rows, as the reference's probs).
-        Returns (info [B, K] uint8, xhat [B, N] uint8).  The rows go in one pass into the tiled root
-        layout (pcub_tile_pairs) and through the headline kernel (decode_tiled_native); the same
-        decisions as decode_native on the transposed rows."""
-        B = xy.shape[0]
-        T = bin_tile(self.code.n)
-        info_w, xh_w, _ = self.decode_tiled_native(tile_pairs(xy, T), B)
+        Returns (info [B, K] uint8, xhat [B, N] uint8).  The kernels read the rows in place
+        (decode_rows_native) wherever that is also the faster path (rows_preferred: N <= 64 and
+        N = 512 .. 16384 with the default variants); elsewhere the rows still go through the tiled
+        layout (pcub_tile_pairs, decode_tiled_native).  The same decisions as decode_native on the
+        transposed rows either way."""
+        if rows_preferred(self.code.n):
+            info_w, xh_w, _ = self.decode_rows_native(xy)
+        else:
+            info_w, xh_w, _ = self.decode_tiled_native(tile_pairs(xy, bin_tile(self.code.n)), xy.shape[0])
         return unpack(info_w, self.code.K), unpack(xh_w, self.code.N)
 
 
@@ -540,11 +574,27 @@ class QaryDecoder:
         _lib.check(rc, "pcub_sc_decode_qary_tiled")
         return info[:c.K], xh
 
-    def decode(self, xy):
-        """xy: [B, N, q] float64 -> (info [B, K] uint8, xhat [B, N] uint8), through the tiled layout
-        (pcub_tile_pairs, decode_tiled_native)."""
+    def decode_rows_native(self, xy, want_xhat=True):
+        """xy: [B, N, q] float64 on device (per-codeword rows), read in place (pcub_sc_decode_qary_rows):
+        the same decode as decode_native on the transposed rows -> (info [K, B] uint8, xhat [N, B] uint8
+        | None)."""
+        c = self.code
+        if xy.dtype != torch.float64 or xy.dim() != 3 or xy.shape[1] != c.N or xy.shape[2] != c.q or not xy.is_cuda:
+            raise ValueError("xy must be a float64 [B, N, q] device tensor with N=%d, q=%d" % (c.N, c.q))
+        xy = xy.contiguous()
         B = xy.shape[0]
-        info, xh = self.decode_tiled_native(tile_pairs(xy, self.tile()), B)
+        info = torch.empty((max(1, c.K), B), dtype=torch.uint8, device=xy.device)
+        xh = torch.empty((c.N, B), dtype=torch.uint8, device=xy.device) if want_xhat else None
+        ws = self.workspace(B)
+        rc = _lib.lib().pcub_sc_decode_qary_rows(_p(xy), B, c.n, c.q, _p(c.frozen_dev), c.K, _p(info), _p(xh), _p(ws),
+                                                 ws.numel(), _stream())
+        _lib.check(rc, "pcub_sc_decode_qary_rows")
+        return info[:c.K], xh
+
+    def decode(self, xy):
+        """xy: [B, N, q] float64 -> (info [B, K] uint8, xhat [B, N] uint8); the kernels read the rows in
+        place (decode_rows_native)."""
+        info, xh = self.decode_rows_native(xy)
         return info.t().contiguous(), xh.t().contiguous()
 
 
