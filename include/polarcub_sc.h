@@ -281,6 +281,26 @@ int pcub_sc_prior_bin(const double* xy, const double* px, int64_t px_batch, int6
  * m = p / s, (0.5, 0.5) when s = 0.  count values in, [count][2] f64 out. */
 int pcub_leaf_marginals(const double* leaf, int64_t count, double* marginals, void* stream);
 
+/* Genie trials under a non-uniform a-priori distribution (genieSingleEncodeSimulatioan /
+ * genieSingleDecodeSimulatioan, BinaryPolarEncoderDecoder.py:114-221): every position frozen, a
+ * fresh common randomness for every trial (geniePreSteps, :101-107), so u_i = 0 iff the prior
+ * leaf's marginal m0 >= r[b][i] (:258-262) and the xy tree never decides.  One wave a trial, the
+ * stage levels of both trees in the wave's LDS; no workspace.  All layouts are per-trial rows:
+ *   xy           [B][N][2] f64 joint pairs (the genie decoder), or NULL (the genie encoder: only
+ *                the prior tree runs)
+ *   prior        [prior_batch][N][2] f64 prior pairs, prior_batch = 1 (one prior) or B
+ *   r            [B][N] f64 common randomness of each trial
+ *   xhat, u      [B][N] u8 re-encoded bits and decisions; either may be NULL
+ *   leaf         [B][N] compact leaves of the xy tree (the prior tree when xy is NULL);
+ *                pcub_leaf_marginals turns them into marginalizedUProbs (:267-273)
+ * log2N in 1..13 (the LDS of one wave: 16 (N - 2) + N bytes with xy); pcub_sc_genie_prior_supported
+ * returns 1 for a length the kernel takes (with_xy: the decoder), else 0.  PCUB_EINVAL before any
+ * HIP call: log2N outside 1..13, B < 0, prior_batch not 1 or B, NULL prior, r or leaf.  B = 0
+ * returns 0 and launches nothing. */
+int pcub_sc_genie_prior_supported(int32_t log2N, int32_t with_xy);
+int pcub_sc_genie_prior_bin(const double* xy, const double* prior, int64_t prior_batch, const double* r, int64_t B,
+                            int32_t log2N, uint8_t* xhat, uint8_t* u, double* leaf, void* stream);
+
 /* Binary SC decode of compact normalised rows: xc [N][B] f64, +r standing for the joint row
  * (1, r) and -r for (r, 1) (NaN: (0, 0)).  The same decode as pcub_sc_decode_bin on those pairs
  * (the reference's arithmetic on a row with a 1 in it is the compact one), from 8 bytes a position

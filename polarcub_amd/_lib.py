@@ -126,6 +126,11 @@ def lib():
                                     _c_void_p, _c_void_p, _c_void_p, ctypes.c_size_t, _c_void_p]
     L.pcub_leaf_marginals.restype = ctypes.c_int
     L.pcub_leaf_marginals.argtypes = [_c_void_p, _i64, _c_void_p, _c_void_p]
+    L.pcub_sc_genie_prior_supported.restype = ctypes.c_int
+    L.pcub_sc_genie_prior_supported.argtypes = [_i32, _i32]
+    L.pcub_sc_genie_prior_bin.restype = ctypes.c_int
+    L.pcub_sc_genie_prior_bin.argtypes = [_c_void_p, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p, _c_void_p,
+                                          _c_void_p, _c_void_p]
     _u64 = ctypes.c_uint64
     L.pcub_mc_info.restype = ctypes.c_int
     L.pcub_mc_info.argtypes = [_u64, _i64, _i64, _i32, _c_void_p, _c_void_p]
@@ -237,7 +242,8 @@ EXPORTS = ["pcub_abi_version", "pcub_sc_decode_bin_workspace", "pcub_sc_decode_b
            "pcub_mc_run_qary_workspace", "pcub_mc_run_qary", "pcub_mc_run_deletion_workspace", "pcub_mc_run_deletion",
            "pcub_ir_prepare", "pcub_ir_classify", "pcub_mc_run_ir_workspace", "pcub_mc_run_ir",
            "pcub_genie_count", "pcub_mc_genie_deletion_workspace", "pcub_mc_genie_deletion",
-           "pcub_sc_decode_bin_rows", "pcub_sc_decode_qary_rows", "pcub_sc_bin_rows_preferred"]
+           "pcub_sc_decode_bin_rows", "pcub_sc_decode_qary_rows", "pcub_sc_bin_rows_preferred",
+           "pcub_sc_genie_prior_supported", "pcub_sc_genie_prior_bin"]
 
 
 def check(rc, what):

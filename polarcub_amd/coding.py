@@ -26,7 +26,17 @@ frozen bits drawn against the common randomness).  Any other plugin (other
 trellis shapes, user classes, non-memoryless priors) goes through
 recursiveEncodeDecode, which drives the plugin's own methods exactly as the
 reference does.  Additions: decode_batch / encode_batch / decode_deletion_batch /
-decode_prior_batch / encode_prior_batch.
+decode_prior_batch / encode_prior_batch / genie_encode_prior_batch /
+genie_decode_prior_batch.
+
+genieEncodeDecodeSimulation batches its trials on the GPU: under a uniform prior
+through the leaf-export kernels, and under a non-uniform memoryless prior
+(N = 2 .. 8192, a usable GPU) through pcub_sc_genie_prior_bin -- the encoder pass
+of a chunk as one batch, the decoder pass of its memoryless-xy trials as another,
+each trial against its own common randomness.  Without a GPU, beyond N = 8192 or
+with any other xy plugin those trials take the per-trial host recursion
+(genieSingleEncodeSimulatioan / genieSingleDecodeSimulatioan, which are never
+rerouted themselves).
 """
 import random
 import sys
@@ -163,6 +173,48 @@ class BinaryPolarEncoderDecoder:
         inf = torch.as_tensor(np.asarray(information, dtype=np.uint8).reshape(-1, self.k), device=dev)
         return pc.encode(torch.as_tensor(np.asarray(prior, dtype=np.float64), device=dev), inf).cpu().numpy().astype(
             np.int64)
+
+    def genie_encode_prior_batch(self, prior, seeds, R=None):
+        """genieSingleEncodeSimulatioan(xvd, seed) for every seed as one device batch
+        (pcub_sc_genie_prior_bin): prior [N, 2] (or [B, N, 2] per trial).  Returns, per trial, what
+        the per-trial method returns: (encoded int64[N], TVvec, Hvec).  R [B, N]: the trials' common
+        randomness when the caller has drawn it already."""
+        import torch
+
+        from . import sc
+        R = _genie_r(self.length, seeds) if R is None else R
+        gp = sc.GeniePriorCoder(self.length)
+        xh, _, m = gp.encode(torch.from_numpy(np.ascontiguousarray(prior, dtype=np.float64)), torch.from_numpy(R))
+        xh = xh.cpu().numpy().astype(np.int64)
+        out = []
+        # the marginals stay numpy scalars, as the host recursion's are: the sums the simulation
+        # prints then have the same element types (and repr) as the per-trial path's
+        for t, mt in enumerate(m.cpu().numpy()):
+            out.append((xh[t], [abs(m0 - m1) for m0, m1 in mt], [eta(m0) + eta(m1) for m0, m1 in mt]))
+        return out
+
+    def genie_decode_prior_batch(self, prior, xy, seeds, trustXYProbs=True, R=None):
+        """genieSingleDecodeSimulatioan(xvd, xyvd, seed, trustXYProbs) for memoryless xy [B, N, 2] as
+        one device batch.  Returns, per trial, (decoded int64[N], Pevec, Hvec)."""
+        import torch
+
+        from . import sc
+        R = _genie_r(self.length, seeds) if R is None else R
+        gp = sc.GeniePriorCoder(self.length)
+        xh, u, m = gp.decode(torch.from_numpy(np.ascontiguousarray(prior, dtype=np.float64)),
+                             torch.from_numpy(np.ascontiguousarray(_check_joint(xy))), torch.from_numpy(R))
+        xh = xh.cpu().numpy().astype(np.int64)
+        u = u.cpu().numpy().astype(np.int64)
+        m = m.cpu().numpy()
+        out = []
+        for t in range(len(xh)):
+            if trustXYProbs:  # numpy scalars, as in genieSingleDecodeSimulatioan (see the encoder above)
+                pe = [min(m0, m1) for m0, m1 in m[t]]
+                h = [eta(m0) + eta(m1) for m0, m1 in m[t]]
+            else:
+                pe, h = _genie_stats(m[t], u[t], False)
+            out.append((xh[t], pe, h))
+        return out
 
     def decode_batch(self, xy):
         """xy: [B, N, 2] joint probabilities (numpy or torch), uniform prior.
@@ -416,6 +468,31 @@ def _genie_u(length, seed):
     return np.array([0 if 0.5 >= rng.random() else 1 for _ in range(length)], np.uint8)
 
 
+def _genie_r(length, seeds):
+    """The genie's common randomness [T, N], one row a trial: the MT19937 draws of Random(seed), or
+    all ones for seed -1 (geniePreSteps, BinaryPolarEncoderDecoder.py:101-107 over :33-44)."""
+    R = np.ones((len(seeds), length))
+    for t, seed in enumerate(seeds):
+        if seed != -1:
+            rng = random.Random()
+            rng.seed(seed)
+            R[t] = [rng.random() for _ in range(length)]
+    return R
+
+
+def _genie_device_prior(xvd, length):
+    """The prior rows [N, 2] when the genie under this non-uniform prior runs on the device
+    (a memoryless binary prior, a usable GPU, a length pcub_sc_genie_prior_bin takes), else None."""
+    p = _prior_rows(xvd, length)
+    if p is None:
+        return None
+    import torch
+    if not torch.cuda.is_available():
+        return None
+    from . import sc
+    return p if sc.genie_prior_supported(length) else None
+
+
 def _genie_stats(m, u, trustXYProbs):
     """Pe / H of one genie decode from its leaf marginals m [N, 2] and the genie's u
     (genieSingleDecodeSimulatioan, BinaryPolarEncoderDecoder.py:114-178)."""
@@ -439,13 +516,17 @@ def genieEncodeDecodeSimulation(length, make_xVectorDistribution, make_codeword,
     host in trial order (consuming their RNGs exactly as the reference does); under a
     uniform prior the genie encoder is the GPU polar transform and the genie decodes of
     memoryless and deletion-collection trials run on the GPU with every leaf exported
-    (pcub_sc_leaf_bin / pcub_sc_leaf_deletion, per-trial frozen values).  Other plugins
-    use the generic per-trial recursion.  Statistics are accumulated in trial order."""
+    (pcub_sc_leaf_bin / pcub_sc_leaf_deletion, per-trial frozen values); under a non-uniform
+    memoryless prior the device takes (_genie_device_prior) the chunk's genie encodes are one
+    batch and the genie decodes of its memoryless trials another (pcub_sc_genie_prior_bin, each
+    trial against its own common randomness).  Other plugins use the generic per-trial
+    recursion.  Statistics are accumulated in trial order."""
     xvd = make_xVectorDistribution()
     encDec = BinaryPolarEncoderDecoder(length, set(), 0)
     seed_rng = random.Random()
     seed_rng.seed(genieSeed)
     uniform = _is_uniform_prior(xvd)
+    prior = None if uniform else _genie_device_prior(xvd, length)
     TV = Pe = HEnc = HDec = None
     codeword = []
     chunk = 1 << 12
@@ -453,17 +534,22 @@ def genieEncodeDecodeSimulation(length, make_xVectorDistribution, make_codeword,
         T = min(chunk, numberOfTrials - t0)
         seeds = [seed_rng.randint(1, 1000000) for _ in range(T)]
         enc_stats = []
+        R = None
         if uniform:
             U = np.stack([_genie_u(length, s) for s in seeds])
             enc_all = BinaryPolarEncoderDecoder(length, set(), 0).encode_batch(U)  # K = N: x = polar(u)
             h_half = eta(0.5) + eta(0.5)
             for t in range(T):
                 enc_stats.append((enc_all[t], [abs(0.5 - 0.5)] * length, [h_half] * length))
+        elif prior is not None:
+            U = None
+            R = _genie_r(length, seeds)
+            enc_stats = encDec.genie_encode_prior_batch(prior, seeds, R=R)
         else:
             U = None
             for s in seeds:
                 enc_stats.append(encDec.genieSingleEncodeSimulatioan(xvd, s))
-        items, bin_rows, del_rows = [], [], {}
+        items, bin_rows, del_rows, prior_rows = [], [], {}, []
         for t in range(T):
             codeword = make_codeword(enc_stats[t][0])
             received = simulateChannel(codeword)
@@ -472,6 +558,9 @@ def genieEncodeDecodeSimulation(length, make_xVectorDistribution, make_codeword,
             if uniform and _is_memoryless_binary(xyvd) and length >= 2:
                 items.append(("bin", len(bin_rows)))
                 bin_rows.append(_check_joint(xyvd.probs))
+            elif prior is not None and _is_memoryless_binary(xyvd) and np.shape(xyvd.probs) == (length, 2):
+                items.append(("prior", len(prior_rows)))
+                prior_rows.append((t, _check_joint(xyvd.probs)))
             elif shape is not None:
                 rows = del_rows.setdefault(shape, [])
                 items.append((shape, len(rows)))
@@ -484,10 +573,17 @@ def genieEncodeDecodeSimulation(length, make_xVectorDistribution, make_codeword,
                                                                             if it[0] == "bin"]])
         for shape, rows in del_rows.items():
             marg[shape] = _device_genie_deletion(length, shape, [w for _, w in rows], U[[t for t, _ in rows]])
+        prior_dec = []
+        if prior_rows:
+            ts = [t for t, _ in prior_rows]
+            prior_dec = encDec.genie_decode_prior_batch(prior, np.stack([p for _, p in prior_rows]),
+                                                        [seeds[t] for t in ts], trustXYProbs, R=R[ts])
         for t in range(T):
             kind, val = items[t]
             if kind == "host":
                 _, pe, hdec = val
+            elif kind == "prior":
+                _, pe, hdec = prior_dec[val]
             else:
                 pe, hdec = _genie_stats(marg[kind][val], U[t], trustXYProbs)
             _, tv, henc = enc_stats[t]

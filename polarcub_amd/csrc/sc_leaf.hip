@@ -18,6 +18,7 @@
 
 #include "polarcub_sc.h"
 #include "sc_common.h"
+#include "sc_leaf_common.h"
 
 using namespace pcub;
 
@@ -39,8 +40,6 @@ struct LeafArgs {
     uint8_t* ybits;             // [N][nslots]
     long long nslots;
 };
-
-PCUB_HD uint32_t word_bit(const uint32_t* w, int i) { return (w[i >> 5] >> (i & 31)) & 1u; }
 
 __device__ void leaf_cw(const LeafArgs& A, long long cw, long long slot, bool store) {
     const int n = A.n;
@@ -161,17 +160,6 @@ struct PriorArgs {
     uint8_t* ybits;          // [N][nslots]
     long long nslots;
 };
-
-// the reference's marginal m0 of a compact normalised leaf (calcMarginalizedProbabilities, :52-69)
-PCUB_HD double leaf_m0(double v) {
-    const CV c = cv_load(v);
-    double p0 = c.s ? c.r : 1.0, p1 = c.s ? 1.0 : c.r;
-    if (c.r != c.r) p0 = p1 = 0.0;
-    double s = 0.0;
-    s += p0;
-    s += p1;
-    return s > 0.0 ? p0 / s : 0.5;
-}
 
 template <bool XY>
 __device__ void prior_cw(const PriorArgs& A, long long cw, long long slot, bool store) {

@@ -440,6 +440,82 @@ def leaf_marginals(leaf):
     return m
 
 
+def genie_prior_supported(N, with_xy=True):
+    """True when pcub_sc_genie_prior_bin takes code length N (2 .. 8192: one wave's LDS holds the
+    stage levels of both trees)."""
+    N = int(N)
+    if N < 2 or N & (N - 1):
+        return False
+    return bool(_lib.lib().pcub_sc_genie_prior_supported(N.bit_length() - 1, int(bool(with_xy))))
+
+
+class GeniePriorCoder:
+    """Genie trials under a non-uniform a-priori distribution (pcub_sc_genie_prior_bin): every
+    position frozen, a fresh common randomness R[b] for every trial, the prior tree deciding every
+    u_i (genieSingleEncodeSimulatioan / genieSingleDecodeSimulatioan,
+    BinaryPolarEncoderDecoder.py:114-221).  All tensors are per-trial rows: prior [N, 2] (one for
+    the batch) or [B, N, 2], xy [B, N, 2], R [B, N], float64 on the device."""
+
+    def __init__(self, N, device=None):
+        self.N = int(N)
+        self.n = _log2(self.N)
+        if not genie_prior_supported(self.N):
+            raise ValueError("the genie kernel under a prior takes N = 2 .. 8192, got %d" % self.N)
+        self.device = torch.device("cuda") if device is None else torch.device(device)
+
+    def _rows(self, t, shape, what):
+        t = torch.as_tensor(t, dtype=torch.float64, device=self.device)
+        if tuple(t.shape) != shape:
+            raise ValueError("%s must be float64 %s, got %s" % (what, list(shape), list(t.shape)))
+        return t.contiguous()
+
+    def run_native(self, prior, R, xy=None):
+        """Returns (xhat [B, N] uint8, u [B, N] uint8, leaf [B, N] compact leaves of the xy tree, or
+        of the prior tree without xy)."""
+        N = self.N
+        R = torch.as_tensor(R, dtype=torch.float64, device=self.device)
+        if R.dim() != 2 or R.shape[1] != N:
+            raise ValueError("R must be float64 [B, N] with N=%d" % N)
+        R = R.contiguous()
+        B = R.shape[0]
+        prior = torch.as_tensor(prior, dtype=torch.float64, device=self.device)
+        if prior.dim() == 2:
+            prior = prior[None]
+        if prior.dim() != 3 or prior.shape[0] not in (1, B) or tuple(prior.shape[1:]) != (N, 2):
+            raise ValueError("prior must be float64 [N, 2], [1, N, 2] or [B, N, 2] with N=%d" % N)
+        prior = prior.contiguous()
+        if xy is not None:
+            xy = self._rows(xy, (B, N, 2), "xy")
+        xhat = torch.empty((B, N), dtype=torch.uint8, device=self.device)
+        u = torch.empty((B, N), dtype=torch.uint8, device=self.device)
+        leaf = torch.empty((B, N), dtype=torch.float64, device=self.device)
+        if B == 0:
+            return xhat, u, leaf
+        # one prior for a batch of one trial: prior_batch = 1 = B either way
+        rc = _lib.lib().pcub_sc_genie_prior_bin(_p(xy), _p(prior), prior.shape[0], _p(R), B, self.n, _p(xhat), _p(u),
+                                                _p(leaf), _stream())
+        _lib.check(rc, "pcub_sc_genie_prior_bin")
+        return xhat, u, leaf
+
+    @staticmethod
+    def _marginals(leaf):
+        m = torch.empty(tuple(leaf.shape) + (2,), dtype=torch.float64, device=leaf.device)
+        _lib.check(_lib.lib().pcub_leaf_marginals(_p(leaf), leaf.numel(), _p(m), _stream()), "pcub_leaf_marginals")
+        return m
+
+    def encode(self, prior, R):
+        """The genie encoder: (xhat [B, N] uint8, u [B, N] uint8, m_x [B, N, 2] prior-tree leaf marginals)."""
+        xhat, u, leaf = self.run_native(prior, R)
+        return xhat, u, self._marginals(leaf)
+
+    def decode(self, prior, xy, R):
+        """The genie decoder: (xhat, u, m_xy [B, N, 2] xy-tree leaf marginals)."""
+        if xy is None:
+            raise ValueError("decode needs xy [B, N, 2]")
+        xhat, u, leaf = self.run_native(prior, R, xy=xy)
+        return xhat, u, self._marginals(leaf)
+
+
 def transpose_pairs(xy):
     """[B, N, q] float64 -> [N, B, q] float64 on device."""
     if xy.dtype != torch.float64 or xy.dim() != 3:
