@@ -466,6 +466,54 @@ int pcub_mc_genie_deletion(uint64_t seed, int64_t offset, int64_t count, int32_t
                            int32_t W, int32_t ones, double pd, int64_t chunk, uint64_t* counters, void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* Genie construction over a binary memoryless channel as one device pipeline: the uniform-prior,
+ * every-position-frozen-to-u case of recursiveEncodeDecode (BinaryPolarEncoderDecoder.py:223-325, as
+ * genieSingleDecodeSimulatioan calls it, :114-178) with the statistic of trustXYProbs = False.
+ *   pcub_sc_genie_bin  one batch, decoded breadth-first and counted in the kernel.  Every u_i is
+ *     given, so no value waits for a decision: the SC tree is evaluated level by level (log2 N passes
+ *     of N values, op_f / op_g / op_f_raw / op_g_raw of the SC decode on every pair), a workgroup a
+ *     trial, the levels in its LDS; each leaf is classified where it appears (pcub_genie_count's
+ *     classes) and the counts stay in LDS over all the trials a workgroup takes; one 64-bit atomic a
+ *     non-zero count a workgroup at the end of the launch.
+ *       rows      per-trial rows: compact == 0: [B][N][2] f64 joint pairs (the reference's probs; the
+ *                 root is never normalised); compact != 0: [B][N] f64 compact normalised rows (+r =
+ *                 (1, r), -r = (r, 1), NaN = (0, 0)), what pcub_mc_channel_norm_tiled writes with
+ *                 compact = 1, tile = 1.  A trial's row is one contiguous run, read in address order.
+ *       u_words   [ceil(N/32)][B] the true bits (pcub_mc_info's layout with K = N)
+ *       counters  device u64[1 + 2N], pcub_genie_count's layout, accumulating; the caller zeroes them
+ *       leaf      NULL, or [N][B] f64: the compact leaves, the layout pcub_sc_leaf_bin writes (for
+ *                 pcub_leaf_marginals / pcub_genie_count).  With NULL nothing of size N B is written.
+ *     The leaves equal pcub_sc_leaf_bin's with every position frozen to u, bit for bit, and the
+ *     counters equal pcub_genie_count's on them.  log2N in 1..13 (16 N + N / 4 bytes of LDS a
+ *     workgroup); pcub_sc_genie_bin_supported(log2N) is 1 for those, else 0.  PCUB_EINVAL before any
+ *     HIP call: an unsupported length, NULL rows / u_words / counters, B < 0 or above 2^30 (a
+ *     workgroup's 32-bit counts must not wrap; split longer batches).  B = 0 returns 0 and
+ *     launches nothing.  pcub_sc_genie_bin_geom is the same call with the workgroup size given
+ *     (64, 256 or 1024 work items; 0: the default for the length) -- a measurement hook; the result
+ *     does not depend on it.
+ *   pcub_mc_genie_bin  for trials [offset, offset + count), chunk at a time on the stream, no host
+ *     synchronisation: u = pcub_mc_info (K = N) -> pcub_polar_encode_bin (no frozen position) ->
+ *     pcub_mc_channel_norm_tiled (channel 0 = BI-AWGN, param = sigma^2 > 0; 1 = BSC, param = p in
+ *     [0, 1]; compact rows, tile = 1: per-trial rows, no transposition pass) -> pcub_sc_genie_bin
+ *     (no leaf buffer).  Trial g's u and row are those of pcub_mc_info / pcub_mc_channel_norm at the
+ *     same (seed, g), so any sharding or chunking of the range gives the same counters.  Past
+ *     log2N = 13 (up to 20) the call composes pcub_mc_channel_norm (pairs) -> pcub_sc_leaf_bin ->
+ *     pcub_genie_count in its workspace.  Workspace: pcub_mc_genie_bin_workspace(chunk, log2N) bytes
+ *     (u, x, the chunk's rows -- 8 N bytes a trial -- and a constant mask; past 13 the pairs, the
+ *     leaves and the leaf kernel's scratch as well, which needs a device to size); 0 for arguments
+ *     it cannot size.  PCUB_EINVAL before any launch: NULL counters / workspace, negative count or
+ *     offset, chunk <= 0, log2N outside 1..20, a channel other than 0 / 1, a param that is not
+ *     finite or outside the channel's domain, a workspace that is too small.  count = 0 returns 0
+ *     and launches nothing.  Counters accumulate; the caller zeroes them. */
+int pcub_sc_genie_bin_supported(int32_t log2N);
+int pcub_sc_genie_bin(const double* rows, int32_t compact, const uint32_t* u_words, int64_t B, int32_t log2N,
+                      uint64_t* counters, double* leaf, void* stream);
+int pcub_sc_genie_bin_geom(const double* rows, int32_t compact, const uint32_t* u_words, int64_t B, int32_t log2N,
+                           int32_t block, uint64_t* counters, double* leaf, void* stream);
+size_t pcub_mc_genie_bin_workspace(int64_t chunk, int32_t log2N);
+int pcub_mc_genie_bin(uint64_t seed, int64_t offset, int64_t count, int32_t log2N, int32_t channel, double param,
+                      int64_t chunk, uint64_t* counters, void* workspace, size_t workspace_bytes, void* stream);
+
 /* [B][nbits] u8 (0/1) -> ceil(nbits/32) x B words, and back. */
 int pcub_pack_bits(const uint8_t* bits, int64_t B, int32_t nbits, uint32_t* words, void* stream);
 int pcub_unpack_bits(const uint32_t* words, int64_t B, int32_t nbits, uint8_t* bits, void* stream);

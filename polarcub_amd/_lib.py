@@ -219,6 +219,17 @@ def lib():
     L.pcub_mc_genie_deletion.restype = ctypes.c_int
     L.pcub_mc_genie_deletion.argtypes = [_u64, _i64, _i64, _i32, _i32, _c_void_p, _i32, _i32, ctypes.c_double, _i64,
                                          _c_void_p, _c_void_p, ctypes.c_size_t, _c_void_p]
+    L.pcub_sc_genie_bin_supported.restype = ctypes.c_int
+    L.pcub_sc_genie_bin_supported.argtypes = [_i32]
+    L.pcub_sc_genie_bin.restype = ctypes.c_int
+    L.pcub_sc_genie_bin.argtypes = [_c_void_p, _i32, _c_void_p, _i64, _i32, _c_void_p, _c_void_p, _c_void_p]
+    L.pcub_sc_genie_bin_geom.restype = ctypes.c_int
+    L.pcub_sc_genie_bin_geom.argtypes = [_c_void_p, _i32, _c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p, _c_void_p]
+    L.pcub_mc_genie_bin_workspace.restype = ctypes.c_size_t
+    L.pcub_mc_genie_bin_workspace.argtypes = [_i64, _i32]
+    L.pcub_mc_genie_bin.restype = ctypes.c_int
+    L.pcub_mc_genie_bin.argtypes = [_u64, _i64, _i64, _i32, _i32, ctypes.c_double, _i64, _c_void_p, _c_void_p,
+                                    ctypes.c_size_t, _c_void_p]
     if L.pcub_abi_version() != ABI_VERSION:
         raise ImportError("libpolarcub_hip.so ABI mismatch; rebuild with python -m polarcub_amd.build --force")
     _lib = L
@@ -243,7 +254,9 @@ EXPORTS = ["pcub_abi_version", "pcub_sc_decode_bin_workspace", "pcub_sc_decode_b
            "pcub_ir_prepare", "pcub_ir_classify", "pcub_mc_run_ir_workspace", "pcub_mc_run_ir",
            "pcub_genie_count", "pcub_mc_genie_deletion_workspace", "pcub_mc_genie_deletion",
            "pcub_sc_decode_bin_rows", "pcub_sc_decode_qary_rows", "pcub_sc_bin_rows_preferred",
-           "pcub_sc_genie_prior_supported", "pcub_sc_genie_prior_bin"]
+           "pcub_sc_genie_prior_supported", "pcub_sc_genie_prior_bin",
+           "pcub_sc_genie_bin_supported", "pcub_sc_genie_bin", "pcub_sc_genie_bin_geom",
+           "pcub_mc_genie_bin_workspace", "pcub_mc_genie_bin"]
 
 
 def check(rc, what):

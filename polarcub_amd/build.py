@@ -31,7 +31,7 @@ SOURCES = ["sc_del_w4.hip", "sc_del_w5.hip", "sc_del_dense.hip", "sc_del_n4w.hip
            "sc_bin.hip", "sc_bin_k0.hip", "sc_bin_k1.hip", "sc_bin_k2.hip", "sc_bin_k4.hip", "sc_bin_k5.hip", "sc_bin_k6.hip", "sc_bin_k7.hip", "sc_bin_k8.hip", "sc_bin_k9.hip", "sc_bin_k10.hip", "sc_bin_k11.hip", "sc_qary.hip",
            "sc_qary_q2.hip", "sc_qary_q3.hip", "sc_qary_q4.hip", "sc_qary_q4r.hip", "sc_qary_q56.hip", "sc_qary_q78.hip",
            "sc_util.hip", "sc_del.hip", "sc_leaf.hip", "sc_qary_log.hip", "scl.hip", "scl_wg.hip",
-           "sc_mc.hip", "sc_ir.hip", "sc_genie.hip", "sc_genie_prior.hip"]
+           "sc_mc.hip", "sc_ir.hip", "sc_genie.hip", "sc_genie_prior.hip", "sc_genie_bin.hip"]
 # compile order only (the link order is SOURCES'): the units that take minutes each, longest first
 SLOWEST_FIRST = ["sc_bin_k9.hip", "sc_bin_k6.hip", "sc_bin_k11.hip", "sc_qary_q4.hip", "sc_qary_q78.hip", "sc_bin_k8.hip",
                  "sc_qary_q56.hip", "sc_bin_k10.hip", "sc_bin_k7.hip", "sc_qary_q4r.hip", "sc_del_n4o.hip", "sc_del_n4x.hip", "sc_qary_q3.hip"]

@@ -715,6 +715,56 @@ def genieEncodeDecodeSimulationDevice(n, n0, xi, pd, numberOfTrials, errorUpperB
     return frozenSet
 
 
+def genieEncodeDecodeSimulationDeviceBin(n, channel, param, numberOfTrials, errorUpperBoundForFrozenSet, genieSeed,
+                                         filename=None):
+    """genieEncodeDecodeSimulation over a binary memoryless channel as one device pipeline
+    (mc.run_genie_bin: the draws, the channel rows, the breadth-first decode with u known and the
+    statistic all stay on the GPU; only 2N + 1 integer counters come back).  channel:
+    mc.CHANNEL_AWGN (param = sigma^2) or mc.CHANNEL_BSC (param = p).  Returns the frozen set, prints
+    the reference's `pevec`, `code rate` and `codeword length` lines (codeword length N) and
+    optionally writes the frozen-bits file in the reference's format.
+
+    The statistic is the untrusted one (trustXYProbs = False): a trial adds 0, 0.5 or 1 to Pe[i];
+    on a memoryless channel its expectation is the trusted statistic's, E[min(m0, m1)], with a
+    larger variance.  TV is 0 under the uniform prior and the TV and H lines are not printed.  As in
+    genieEncodeDecodeSimulationDevice the trials are Philox trials keyed by (genieSeed, trial
+    index), not the reference's MT19937 trials, and under torch.distributed each rank runs its
+    slice of [0, numberOfTrials) and the counters are summed: the sum does not depend on the
+    number of ranks."""
+    import torch
+    import torch.distributed as dist
+
+    from . import mc
+    length = 1 << n
+    world, rank = 1, 0
+    device = torch.device("cuda")
+    if dist.is_available() and dist.is_initialized():
+        world, rank = dist.get_world_size(), dist.get_rank()
+        device = torch.device("cuda", torch.cuda.current_device())
+    lo, hi = mc.shard_range(numberOfTrials, rank, world)
+    trials, wrong, tie = mc.run_genie_bin(n, channel, param, genieSeed, lo, hi - lo, device=device)
+    if world > 1:
+        backend_dev = device if dist.get_backend() == "nccl" else None
+        summed, _ = mc.reduce_counters([trials] + wrong.tolist() + tie.tolist(), 0.0, device=backend_dev)
+        trials, wrong, tie = summed[0], summed[1:1 + length], summed[1 + length:]
+    if trials != numberOfTrials:
+        raise RuntimeError("genie pipeline counted %d trials, expected %d" % (trials, numberOfTrials))
+    return _genie_bin_finish(length, trials, wrong, tie, numberOfTrials, errorUpperBoundForFrozenSet, filename)
+
+
+def _genie_bin_finish(length, trials, wrong, tie, numberOfTrials, errorUpperBoundForFrozenSet, filename=None):
+    """Counts -> Pe -> frozen set, the reference's printout and the frozen-bits file."""
+    TV = [0.0] * length
+    Pe = genie_pe_from_counts(trials, wrong, tie)
+    print("pevec = ", Pe)
+    frozenSet = frozenSetFromTVAndPe(TV, Pe, errorUpperBoundForFrozenSet)
+    print("code rate = ", (length - len(frozenSet)) / length)
+    print("codeword length = ", length)
+    if filename is not None:
+        write_frozen_file(filename, frozenSet, numberOfTrials, TV, Pe)
+    return frozenSet
+
+
 def write_frozen_file(filename, frozenSet, numberOfTrials, TVvec, Pevec, argv=None):
     """Frozen-set file format of BinaryPolarEncoderDecoder.py:471-489."""
     with open(filename, "w") as f:

@@ -282,6 +282,42 @@ def run_genie_deletion(n, n0, xi, pd, seed, offset, count, ones=0, chunk=None, d
     return int(c[0]), c[1:1 + N].copy(), c[1 + N:].copy()
 
 
+def genie_bin_default_chunk(n):
+    """Trials a chunk of run_genie_bin by default: a trial's buffers (8 N bytes of compact rows, u and
+    x; past the fused kernel's lengths 32 N bytes of pairs and leaves) and an eighth more for their
+    alignment within coding._GENIE_DEVICE_BYTES, 2^18 at the most."""
+    from . import coding
+    N = 1 << int(n)
+    per_trial = (8 if sc.genie_bin_supported(N) else 32) * N + 8 * ((N + 31) // 32)
+    return max(1, min(1 << 18, coding._GENIE_DEVICE_BYTES // (per_trial + per_trial // 8)))
+
+
+def run_genie_bin(n, channel, param, seed, offset, count, chunk=None, device=None):
+    """The genie construction over a binary memoryless channel as one device pipeline
+    (pcub_mc_genie_bin: the philox_norm_batch generators of the rate-1 code with per-trial rows, the
+    breadth-first decode with every u known, the statistic counted in the kernel) over global trials
+    [offset, offset + count); channel CHANNEL_AWGN (param = sigma^2) or CHANNEL_BSC (param = p).
+    Returns (trials, wrong int64[N], tie int64[N]) as numpy."""
+    from . import _lib
+    L = _lib.lib()
+    n, count = int(n), int(count)
+    N = 1 << n
+    dev = torch.device("cuda" if device is None else device)
+    if chunk is None:
+        chunk = genie_bin_default_chunk(n)
+    chunk = int(max(1, min(chunk, count)))
+    with torch.cuda.device(dev):
+        need = int(L.pcub_mc_genie_bin_workspace(chunk, n))
+        if need == 0:
+            raise ValueError("pcub_mc_genie_bin: no workspace for chunk=%d n=%d" % (chunk, n))
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        counters = torch.zeros(1 + 2 * N, dtype=torch.int64, device=dev)
+        _lib.check(L.pcub_mc_genie_bin(int(seed), int(offset), count, n, int(channel), float(param), chunk,
+                                       sc._p(counters), sc._p(ws), ws.numel(), sc._stream()), "pcub_mc_genie_bin")
+        c = counters.cpu().numpy()
+    return int(c[0]), c[1:1 + N].copy(), c[1 + N:].copy()
+
+
 def ir_prepare(code, seed, offset, B, p, use_log=False):
     """One IR trial's inputs for global codewords [offset, offset + B) (pcub_ir_prepare): the drawn
     word a [N, B] u8, its QSC(p) rows xy [N, B, q] f64 (their logarithms with use_log), and

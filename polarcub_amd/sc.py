@@ -516,6 +516,52 @@ class GeniePriorCoder:
         return xhat, u, self._marginals(leaf)
 
 
+def genie_bin_supported(N):
+    """True when pcub_sc_genie_bin takes code length N (2 .. 8192: a workgroup's LDS holds a level
+    and the counts)."""
+    N = int(N)
+    if N < 2 or N & (N - 1):
+        return False
+    return bool(_lib.lib().pcub_sc_genie_bin_supported(N.bit_length() - 1))
+
+
+class GenieBinCounter:
+    """The genie's untrusted statistic of a batch of memoryless trials under a uniform prior
+    (pcub_sc_genie_bin): every position frozen to the trial's u, the SC tree evaluated breadth-first,
+    every leaf classified against its true bit in the kernel."""
+
+    def __init__(self, N, device=None):
+        self.N = int(N)
+        self.n = _log2(self.N)
+        if not genie_bin_supported(self.N):
+            raise ValueError("the breadth-first genie kernel takes N = 2 .. 8192, got %d" % self.N)
+        self.device = torch.device("cuda") if device is None else torch.device(device)
+
+    def count(self, rows, u_words, compact=False, want_leaf=False, block=0):
+        """rows: per-trial rows on the device, [B, N, 2] float64 joint pairs, or with compact=True
+        [B, N] compact normalised rows; u_words [ceil(N/32), B] int32, the true bits.  Returns
+        (trials, wrong int64[N], tie int64[N]) as numpy, and with want_leaf=True also the compact
+        leaves [N, B] (LeafDecoder.decode_native's layout).  block: the workgroup size (0: the
+        default for N; 64, 256, 1024: a measurement hook, the result is the same)."""
+        N = self.N
+        B = int(rows.shape[0])
+        shape = (B, N) if compact else (B, N, 2)
+        if tuple(rows.shape) != shape or rows.dtype != torch.float64 or not rows.is_cuda:
+            raise ValueError("rows must be a float64 %s device tensor" % list(shape))
+        if tuple(u_words.shape) != ((N + 31) // 32, B) or u_words.dtype != torch.int32 or not u_words.is_cuda:
+            raise ValueError("u_words must be an int32 [ceil(N/32), B] device tensor")
+        rows, u_words = rows.contiguous(), u_words.contiguous()
+        counters = torch.zeros(1 + 2 * N, dtype=torch.int64, device=rows.device)
+        leaf = torch.empty((N, B), dtype=torch.float64, device=rows.device) if want_leaf else None
+        if B:
+            rc = _lib.lib().pcub_sc_genie_bin_geom(_p(rows), 1 if compact else 0, _p(u_words), B, self.n, int(block),
+                                                   _p(counters), _p(leaf), _stream())
+            _lib.check(rc, "pcub_sc_genie_bin")
+        c = counters.cpu().numpy()
+        out = (int(c[0]), c[1:1 + N].copy(), c[1 + N:].copy())
+        return out + (leaf,) if want_leaf else out
+
+
 def transpose_pairs(xy):
     """[B, N, q] float64 -> [N, B, q] float64 on device."""
     if xy.dtype != torch.float64 or xy.dim() != 3:
