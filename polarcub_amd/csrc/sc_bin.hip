@@ -70,14 +70,12 @@ __global__ __launch_bounds__(kBlock) void k_sc_bin_small(BinArgs A) {
     if (cw < A.B) decode_small<NN>(A, cw, true);
 }
 
-typedef BinKernFn KernFn;
-KernFn variant_kernel(int v) {
-    if (KernFn k = bin_kernel_part0(v)) return k;
-    if (KernFn k = bin_kernel_part1(v)) return k;
-    if (KernFn k = bin_kernel_part2(v)) return k;
-    if (KernFn k = bin_kernel_part4(v)) return k;
-    if (KernFn k = bin_kernel_part8(v)) return k;
-    return bin_kernel_part5(v);
+// row I's kernel from its unit, where the row is (v, form)
+template <int... I>
+BinKernFn built_kernel(int v, BinForm f, std::integer_sequence<int, I...>) {
+    BinKernFn k = nullptr;
+    ((kBinBuilt[I].v == v && kBinBuilt[I].form == f ? void(k = bin_unit_kernel<kBinBuilt[I].unit>(v, f)) : void()), ...);
+    return k;
 }
 
 // {32, 4, 2, NT, re-encoded bits in LDS, split last level, prefetch 2}: at N=1024 one stored
@@ -118,7 +116,7 @@ DevInfo dev_info() {
     if (hipDeviceGetAttribute(&d.cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return DevInfo{};
     for (int v = 0; v < kNumVariants; ++v) {
         int occ = 0;
-        const KernFn k = variant_kernel(v);
+        const BinKernFn k = bin_kernel(v, kPairs);
         if (!k || hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k, kBlock, bin_lds_bytes(v)) != hipSuccess ||
             occ < 1)
             occ = 1;
@@ -193,6 +191,10 @@ int pick_variant(int n) {
 
 }  // namespace
 
+BinKernFn pcub::bin_kernel(int v, BinForm f) {
+    return built_kernel(v, f, std::make_integer_sequence<int, kNumBinBuilt>{});
+}
+
 extern "C" int pcub_abi_version(void) { return 4; }
 
 // Tuning hooks (not part of the stable ABI): choose / describe the decode kernel variant.
@@ -212,7 +214,7 @@ extern "C" int pcub_sc_set_max_blocks_per_cu(int b) {
 
 extern "C" int pcub_sc_default_variant(void) { return kDefaultVariant; }
 // Tuning hook (not part of the stable ABI): allow (1, the default) or forbid (0) the uniform-base
-// twins for rows in the wave's own tiles (bin_kernel_tiled_root); returns the previous setting.
+// twins (the Tiled, TiledCompact, Rows and RowsNT forms of kBinBuilt); returns the previous setting.
 extern "C" int pcub_sc_set_tiled_root(int on) {
     const int old = g_tiled_root;
     g_tiled_root = on ? 1 : 0;
@@ -232,7 +234,7 @@ extern "C" int pcub_sc_variant_for(int32_t log2N) {
     return pick_variant(log2N);
 }
 extern "C" int pcub_sc_set_variant(int v) {
-    if (v < 0 || v >= kNumVariants || !variant_kernel(v)) return PCUB_EINVAL;  // not built: EINVAL
+    if (v < 0 || v >= kNumVariants || !bin_kernel(v, kPairs)) return PCUB_EINVAL;  // not built: EINVAL
     g_variant = v;
     return 0;
 }
@@ -247,9 +249,19 @@ extern "C" size_t pcub_sc_decode_bin_workspace(int64_t B, int32_t log2N) {
 
 namespace {
 
-BinKernFn rows_twin(int v, bool nt) {
-    if (BinKernFn k = bin_kernel_rows(v, nt)) return k;
-    return bin_kernel_rows2(v, nt);
+// The form variant v launches in at code length 2^n: rows in the wave's own tiles (tile == 64 / G) run the
+// uniform-base twin where one is built; the caller's [B][N] pairs (rows; tile == 1) run a rows twin where
+// one is built and a wave's block of 64 / G codewords stays inside its 32-bit lane offsets, in the load
+// form pcub_sc_set_rows_nt asks for, or in the other where only one is built.
+BinForm launch_form(int v, int n, int tile, bool rows, bool compact) {
+    const int cww = 64 / kVar[v].G;
+    const BinForm tiled = compact ? kTiledCompact : kTiled;
+    if (g_tiled_root && tile == cww && bin_built(v, tiled)) return tiled;
+    if (rows && g_tiled_root && !compact && ((unsigned long long)cww << n) * sizeof(double2) < (1ull << 32)) {
+        if (bin_built(v, g_rows_nt ? kRowsNT : kRows)) return g_rows_nt ? kRowsNT : kRows;
+        if (bin_built(v, g_rows_nt ? kRows : kRowsNT)) return g_rows_nt ? kRows : kRowsNT;
+    }
+    return compact ? kCompact : kPairs;
 }
 
 // Where reading [B][N] rows in place beats staging them through pcub_tile_pairs (scripts/ab_api_layout.py,
@@ -259,8 +271,7 @@ BinKernFn rows_twin(int v, bool nt) {
 bool rows_preferred(int n) {
     if (n <= 5) return true;
     const int v = pick_variant(n);
-    if (g_tiled_root && (rows_twin(v, false) || rows_twin(v, true))) return true;
-    return kVar[v].T == 0;
+    return launch_form(v, n, 1, true, false) >= kRows || kVar[v].T == 0;
 }
 
 // raw pairs xy, or compact rows xc through a variant's compact-root twin (the caller checks one exists)
@@ -325,18 +336,9 @@ int decode_bin_impl(const double* xy, const double* xc, int64_t B, int32_t log2N
     A.nslots = nslots;
     A.scratch = (double2*)slots;
     A.ybits = kVar[v].Y ? nullptr : (uint32_t*)(slots + (size_t)nslots * (Nv / 2 - bin_sr(v)) * sizeof(double2));
-    // rows in the wave's own tiles: the uniform-base twin where one is instantiated
     BinKernFn kern = nullptr;
     if (g_experiment && tile == 64 / kVar[v].G) kern = exp_kernel(g_experiment, v, xc != nullptr);
-    if (!kern && g_tiled_root && tile == 64 / kVar[v].G) kern = bin_kernel_tiled_root(v, xc != nullptr);
-    if (!kern && g_tiled_root && tile == 64 / kVar[v].G) kern = bin_kernel_tiled_root2(v, xc != nullptr);
-    // the caller's [B][N] rows (tile == 1): the rows twin where one is instantiated and a wave's block of
-    // 64 / G codewords stays inside its 32-bit lane offsets
-    if (!kern && rows && g_tiled_root && !xc && ((64ull / kVar[v].G) << log2N) * sizeof(double2) < (1ull << 32)) {
-        kern = rows_twin(v, g_rows_nt != 0);
-        if (!kern) kern = rows_twin(v, g_rows_nt == 0);  // the other load form where only one is built
-    }
-    if (!kern) kern = xc ? bin_kernel_compact(v) : variant_kernel(v);
+    if (!kern) kern = bin_kernel(v, launch_form(v, log2N, tile, rows, xc != nullptr));
     if (!kern) return PCUB_EINVAL;
     hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(kBlock), launch_lds(v, log2N), st, A);
     return (int)hipGetLastError();
@@ -358,9 +360,24 @@ __global__ __launch_bounds__(kBlock) void k_expand_compact(const double* xc, lon
 
 // the compact path runs a compact-root kernel when the variant picked for 2^n has one (and the
 // code is past the small-code kernels); otherwise the rows are expanded into the workspace
-bool compact_direct(int n) { return n > 5 && bin_kernel_compact(pick_variant(n)) != nullptr; }
+bool compact_direct(int n) { return n > 5 && bin_built(pick_variant(n), kCompact); }
 
 }  // namespace
+
+// Diagnostic hooks (not part of the stable ABI; host-only, no device call).  pcub_sc_bin_form_for: the
+// BinForm number the launcher runs at 2^log2N under the current switches (the experiment hook apart) for
+// pairs in tiles of `tile` codewords (0: untiled), for the caller's rows (rows: tile is not read), or
+// for compact rows (compact: Pairs where they are expanded first); kNumBinForms stands for the
+// small-code kernels (log2N <= 5).  pcub_sc_bin_form_built: 1 where the library builds (v, form), else 0.
+extern "C" int pcub_sc_bin_form_for(int32_t log2N, int32_t tile, int32_t rows, int32_t compact) {
+    if (log2N < 0 || log2N > 24 || tile < 0 || tile > 4096 || (rows && compact)) return PCUB_EINVAL;
+    if (log2N <= 5) return kNumBinForms;
+    return launch_form(pick_variant(log2N), log2N, rows ? 1 : tile, rows != 0, compact && compact_direct(log2N));
+}
+extern "C" int pcub_sc_bin_form_built(int v, int form) {
+    if (v < 0 || v >= kNumVariants || form < 0 || form >= kNumBinForms) return PCUB_EINVAL;
+    return bin_built(v, (BinForm)form);
+}
 
 extern "C" int pcub_sc_decode_bin(const double* xy, int64_t B, int32_t log2N, const uint32_t* frozen_mask,
                                   const uint32_t* frozen_val, int32_t K, uint32_t* info_words, uint32_t* xhat_words,
@@ -389,7 +406,7 @@ extern "C" int pcub_sc_decode_bin_tiled(const double* xy, int64_t B, int32_t log
 
 // The caller's per-codeword rows xy [B][N][2] read in place: the tiled layout of width 1 for the generic
 // kernels (codeword cw's row 0 at element cw N, rows 1 element apart), and the rows twins of the
-// default variants (bin_kernel_rows) where they are built.  No staging pass, no second buffer.
+// default variants (kBinBuilt's Rows, RowsNT) where they are built.  No staging pass, no second buffer.
 extern "C" int pcub_sc_decode_bin_rows(const double* xy, int64_t B, int32_t log2N, const uint32_t* frozen_mask,
                                        const uint32_t* frozen_val, int32_t K, uint32_t* info_words,
                                        uint32_t* xhat_words, uint32_t* u_words, void* workspace,

@@ -1,9 +1,10 @@
-// sc_bin_kern.h -- the binary SC decode kernel template and its variant table.
-//
-// The variants are instantiated in several translation units (sc_bin_k*.hip) so
-// the library builds in parallel; sc_bin.hip owns the launch code.
+// sc_bin_kern.h -- the binary SC decode kernel template, its variant table, and the list of the kernels
+// the library builds (kBinBuilt: which variant in which root form, in which translation unit).
+// sc_bin.hip owns the launch code.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <utility>
 
 #include "sc_bin_sched.h"
 
@@ -81,26 +82,100 @@ __global__ __launch_bounds__(kBinBlock, W) void k_sc_bin(BinArgs A) {
 
 typedef void (*BinKernFn)(BinArgs);
 
-// The kernel of variant v if this translation unit instantiates it, else nullptr.  The shipped library
-// builds the variants pick_variant can launch (0, 1, 10, 13, 14, 17, 24, 26, 31); the rest of kVar
-// are the round 1-3 sweep's geometries, measured slower, kept as table rows so the
-// variant numbers in profiles/ stay meaningful; pcub_sc_set_variant rejects them.
-BinKernFn bin_kernel_part0(int v);
-BinKernFn bin_kernel_part1(int v);
-BinKernFn bin_kernel_part2(int v);
-BinKernFn bin_kernel_part4(int v);
-BinKernFn bin_kernel_part5(int v);
-BinKernFn bin_kernel_part8(int v);
-// the compact-root twin of variant v (CR: root rows as compact normalised doubles), or nullptr
-BinKernFn bin_kernel_compact(int v);
-// variant v reading its root in the wave's own tiles (TR: tile = 64 / G, a wave-uniform base and
-// 32-bit lane offsets), pairs or compact rows; nullptr where not instantiated (sc_bin_k7.hip)
-BinKernFn bin_kernel_tiled_root(int v, bool compact);
-BinKernFn bin_kernel_tiled_root2(int v, bool compact);  // sc_bin_k9.hip: the N >= 4096 variants' twins
-// variant v reading the caller's [B][N] rows in place (RW: a wave's 64 / G codewords are one block of
-// (64 / G) N rows; the same uniform base and 32-bit lane offsets as TR), or nullptr.  nt: the root
-// loads non-temporal as the tiled twins' (else plain; variant 26 has both, sc_bin_k10.hip)
-BinKernFn bin_kernel_rows(int v, bool nt);
-BinKernFn bin_kernel_rows2(int v, bool nt);  // sc_bin_k11.hip: variants 30, 33
+// The root forms a variant can be built in: what the kernel reads at the root of the tree.
+//   Compact      CR: the root rows as compact normalised doubles (the Monte-Carlo pipeline's rows, 8 bytes a
+//                position instead of a 16-byte pair)
+//   Tiled        TR: the rows in the wave's own tiles (tile = 64 / G codewords), addressed from a
+//                wave-uniform base with 32-bit lane offsets; TiledCompact: the same over compact rows
+//   Rows         RW: the caller's [B][N] rows read in place (a wave's 64 / G codewords are one block of
+//                (64 / G) N rows; the same uniform base and lane offsets as Tiled), the root loads plain;
+//                RowsNT: non-temporal as the other forms' (kVar's T)
+enum BinForm { kPairs, kCompact, kTiled, kTiledCompact, kRows, kRowsNT, kNumBinForms };
+
+// The one statement of a kernel's template arguments: variant V's row of kVar; the form decides CR, TR,
+// RW and, for the rows forms, the load hint.
+template <int V, BinForm F>
+constexpr BinKernFn bin_instance() {
+    constexpr Variant r = kVar[V];
+    constexpr bool CR = F == kCompact || F == kTiledCompact, TR = F >= kTiled, RW = F == kRows || F == kRowsNT;
+    return k_sc_bin<r.S, r.G, r.W, r.L != 0, RW ? int(F == kRowsNT) : r.T, r.Y != 0, r.H != 0, r.P, CR, TR, RW>;
+}
+
+// The kernels the library builds, each in the translation unit sc_bin_k<unit>.hip (several units so that
+// the library builds in parallel).  The variants are those pick_variant can launch; the rest of kVar are
+// the round 1-3 sweep's geometries, measured slower, kept as table rows so the variant
+// numbers in profiles/ stay meaningful; pcub_sc_set_variant rejects them.
+struct BinBuilt {
+    int unit, v;
+    BinForm form;
+};
+constexpr BinBuilt kBinBuilt[] = {
+    {0, 0, kPairs}, {0, 24, kPairs},
+    {1, 1, kPairs}, {1, 13, kPairs}, {1, 17, kPairs},
+    {2, 10, kPairs}, {2, 14, kPairs},
+    {4, 26, kPairs},  // the split-level default
+    {5, 31, kPairs},  // the split level with the re-encoded bits in the slot scratch, N = 4096 and 8192
+    // the split level at G = 8 lanes a codeword (S = 32: 64 values a lane, a node of 512 positions), the
+    // re-encoded bits in LDS (30) or in the slot scratch (33).  At N = 4096 the split level is depth 3, so
+    // only levels 1 and 2 are stored (variant 31, G = 4, stores three): the C3 shape's candidates
+    {8, 30, kPairs}, {8, 33, kPairs},
+    {6, 24, kCompact}, {6, 26, kCompact}, {6, 30, kCompact}, {6, 31, kCompact}, {6, 33, kCompact},
+    {7, 26, kTiled}, {7, 26, kTiledCompact},
+    // the N >= 4096 variants' tiled twins
+    {9, 30, kTiled}, {9, 30, kTiledCompact}, {9, 31, kTiled}, {9, 31, kTiledCompact},
+    {9, 33, kTiled}, {9, 33, kTiledCompact},
+    // the default variant (N = 1024, 2048) with both load forms: a 128-byte line of the rows holds eight
+    // rows of one codeword, fetched 16 bytes a load over a pass, and must stay cached until its other pieces
+    // are used -- C2: 17.1 ms plain against 29.3 ms non-temporal (pcub_sc_set_rows_nt picks)
+    {10, 26, kRows}, {10, 26, kRowsNT},
+    // G = 8: a wave's block is 8 codewords; plain root loads only: the non-temporal hint of the tiled twins
+    // costs the rows layout more than twice the decode
+    {11, 30, kRows}, {11, 33, kRows},
+};
+constexpr int kNumBinBuilt = sizeof(kBinBuilt) / sizeof(kBinBuilt[0]);
+
+// the rows of kBinBuilt that build (v, form): 1 where the library has the kernel, else 0
+constexpr int bin_built(int v, BinForm f) {
+    int c = 0;
+    for (const BinBuilt& r : kBinBuilt) c += r.v == v && r.form == f;
+    return c;
+}
+constexpr bool bin_list_sound() {
+    for (const BinBuilt& r : kBinBuilt) {
+        if (r.v < 0 || r.v >= kNumVariants || bin_built(r.v, r.form) != 1) return false;  // no pair twice
+        if (!bin_built(r.v, kPairs)) return false;  // "variant v is built" = its Pairs form is
+        // the launcher takes compact rows only where the variant's Compact form is built (compact_direct)
+        if (r.form == kTiledCompact && !bin_built(r.v, kCompact)) return false;
+    }
+    return true;
+}
+static_assert(bin_list_sound(), "kBinBuilt: a pair twice, a variant without Pairs, or an unreachable compact form");
+
+// Unit U's kernel of (v, form), or nullptr: defined by PCUB_BIN_UNIT(U) in sc_bin_k<U>.hip and nowhere
+// else, so that each unit instantiates its own rows only.
+template <int U>
+BinKernFn bin_unit_kernel(int v, BinForm f);
+// The built kernel of (v, form), or nullptr (sc_bin.hip).
+BinKernFn bin_kernel(int v, BinForm f);
+
+// row I where unit U builds it (the test on U is in a template, so the other units' rows are discarded
+// uninstantiated)
+template <int U, int I>
+void bin_unit_row(int v, BinForm f, BinKernFn& k) {
+    if constexpr (kBinBuilt[I].unit == U)
+        if (kBinBuilt[I].v == v && kBinBuilt[I].form == f) k = bin_instance<kBinBuilt[I].v, kBinBuilt[I].form>();
+}
+template <int U, int... I>
+BinKernFn bin_unit_rows(int v, BinForm f, std::integer_sequence<int, I...>) {
+    BinKernFn k = nullptr;
+    (bin_unit_row<U, I>(v, f, k), ...);
+    return k;
+}
 
 }  // namespace pcub
+
+#define PCUB_BIN_UNIT(U)                                                              \
+    template <>                                                                       \
+    pcub::BinKernFn pcub::bin_unit_kernel<U>(int v, BinForm f) {                      \
+        return bin_unit_rows<U>(v, f, std::make_integer_sequence<int, kNumBinBuilt>{}); \
+    }
